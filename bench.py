@@ -1,12 +1,17 @@
 """Headline benchmark: image-text pairs/s of the XFM-base pre-training step (ITC + ITM + MLM + MIM, 224 px / 30 tokens),
 forward + backward (+ gradient all-reduce for N > 1, + clip/AdamW step), one process per GPU over RCCL.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N > 1: one rank per GPU over torch.distributed.run)
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
+Prints ONE JSON line on rank 0: `metric`, `value` (units per second over the K timed steps), `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (one timed step), the losses of the last step and the configuration.  A plain run does only that: set-up, W warm-up
+steps, K timed steps, the line.  --full adds the figures that take work of their own after the timed region:
   roofline     bf16-MFMA roofline of the dominant kernel (gemm_nt: forward + dgrad GEMMs), from HIP events recorded on
-               the launch stream around every gemm_nt launch of one instrumented step run right after the timed region;
+               the launch stream around every gemm_nt launch of one instrumented step (+ the MFMA work it executes);
+  clocks_under_load, fusion_encoder_fwd_bwd (pre-train), and
   cpu_baseline the CPU oracle (a port, not the reference itself) timed on this host on a bounded sample.
+--dump-outputs DIR writes what the last timed step hands its caller as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -73,7 +78,12 @@ def parse():
                     help="pretrain = BASELINE configs[4] shape, the headline line (default); imagenet / retrieval / vqa / glue = "
                          "configs[1] / [2] / [3] / [0] at their real shapes (secondary lines, same JSON shape)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU leg (0 = short sweep over 8/16/32/64/128)")
+    ap.add_argument("--full", action="store_true", help="also the figures beyond the headline line: instrumented-step roofline and "
+                    "executed MFMA work, clocks under load, fusion-encoder probe, CPU baseline (the --no-* options above trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.batch <= 0:
         a.batch = WORKLOADS[a.workload]["batch"]
     return a
@@ -648,8 +658,139 @@ def device_identity(device):
     return f"{getattr(p, 'pci_domain_id', 0)}:{getattr(p, 'pci_bus_id', -1)}:{getattr(p, 'pci_device_id', -1)}:{device.index}"
 
 
+def instrumented_step(step, wl, rank, ms_per_step):
+    """--full: one more step after the timed region, instrumented -> the line's executed-MFMA-work and roofline fields (rank 0;
+    every rank runs the step, whose collectives pair up across ranks)."""
+    pretrain = wl["name"] == "pretrain"
+    # one instrumented step (outside the timed region): HIP events around every gemm_nt launch on the launch stream
+    # (weight-gradient GEMMs normally run on a second stream; for this step they stay on the launch stream so that an event pair
+    # brackets exactly one kernel's execution instead of a stretch of two overlapping chains); the same step counts the MFMA work the
+    # launched kernels execute (2MNK per GEMM + attention)
+    from xfm_amd.xroberta import _WgradStream
+    import xfm_amd.model_pretrain as mp
+    import xfm_amd.xroberta as xr
+    _WgradStream.enabled, text_on, mp._TEXT_STREAM_ON = False, mp._TEXT_STREAM_ON, False  # (the text tower's stream as well)
+    native, xr._NATIVE_LAYERS = xr._NATIVE_LAYERS, False  # kernel by kernel, so that the wrappers see every launch (same kernels)
+    with FlopCounter() as fc:
+        with GemmTimer() as gt:
+            step()
+    _WgradStream.enabled, mp._TEXT_STREAM_ON, xr._NATIVE_LAYERS = os.environ.get("XFM_WGRAD_STREAM", "1") != "0", text_on, native
+    executed_flop = fc.flop
+    nlaunch, gemm_ms, gemm_flop = gt.summary()
+    dom_n, dom_ms, dom_fl, dom_bytes = gt.dominant()
+    dom_tf = dom_fl / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
+    if os.environ.get("XFM_BENCH_GEMM_SHAPES") and rank == 0:
+        with open(os.environ["XFM_BENCH_GEMM_SHAPES"], "w") as f:
+            for (kind, M, N, K, epi), (calls, ms) in sorted(gt.by_shape().items(), key=lambda kv: -kv[1][1]):
+                tf = "" if kind.startswith("attn") else f"{2.0 * M * N * K * calls / ms / 1e9:6.0f}TF"
+                f.write(f"{kind} M={M:6d} N={N:6d} K={K:6d} epi/bias={epi} calls={calls:3d} total={ms:7.3f}ms avg={ms / calls * 1e3:7.1f}us {tf}\n")
+            for n_items, fl, s_, e_ in gt.groups:
+                gms = s_.elapsed_time(e_)
+                f.write(f"tn_group: {n_items} weight gradients in one grouped launch  total={gms:7.3f}ms  {fl / gms / 1e9:6.0f}TF\n")
+    achieved = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+
+    traffic, traffic_note = None, None
+    if pretrain:
+        for name in ("round4_hbm_traffic.json", "round3_hbm_traffic.json", "round2_hbm_traffic.json", "round1_hbm_traffic.json"):
+            tpath = os.path.join(ROOT, "profiles", name)
+            if os.path.exists(tpath):
+                break
+        for name5 in ("round5_hbm_traffic.json",):
+            if os.path.exists(os.path.join(ROOT, "profiles", name5)):
+                name, tpath = name5, os.path.join(ROOT, "profiles", name5)
+        if os.path.exists(tpath):  # PMC passes are separate rocprofv3 runs of this same command (profiles/README.md)
+            with open(tpath) as f:
+                tj = json.load(f)
+            # every instantiation of the plain-bf16 256 x 256 kernel (round 3: <0, persistent?, look-ahead>; before: <0>)
+            dks = [v for k, v in tj["families"].items() if k.startswith("kernel:gemm_nt_256_kernel<0")]
+            dk = {"hbm_bytes_per_step_corrected": sum(v["hbm_bytes_per_step_corrected"] for v in dks),
+                  "launches_per_step": sum(v["launches_per_step"] for v in dks)} if dks else None
+            if dk and dk["launches_per_step"] > 0:  # the dominant kernel's own launches (its average launch, like `achieved`)
+                traffic = dk["hbm_bytes_per_step_corrected"] / dk["launches_per_step"]
+                traffic_note = f"bytes beyond L2 per launch of gemm_nt_256_kernel<0>, averaged over its {dk['launches_per_step']:.0f} launches per step " \
+                               f"(tail-split row blocks included), from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes in profiles/{name} " \
+                               "(2 x FETCH_SIZE + WRITE_SIZE, KB; tools/pmc_traffic.sh); Infinity-Cache hits are counted; algorithmic bytes " \
+                               f"per launch (A + B + C once) average {dom_bytes / max(dom_n, 1):.3e}"
+                prof_hash, tree_hash = tj.get("kernel_tree_hash"), kernel_tree_hash()
+                traffic_note += (f"; profile taken on kernel tree {prof_hash}, this run's tree is {tree_hash}"
+                                 + ("" if prof_hash == tree_hash else " -- the kernels have changed since the profile (or it predates the stamp): "
+                                    "indicative only, re-run tools/pmc_traffic.sh"))
+    if rank != 0:
+        return {}
+    step_tf_exec = executed_flop / (ms_per_step * 1e-3) / 1e12
+    fams = gt.families()
+    top = max(fams.items(), key=lambda kv: kv[1][1]) if fams else None
+    if not pretrain and top is not None and top[0] != "gemm_nt_256_kernel<EPI_BF16>":
+        # secondary workloads: the roofline is of THEIR dominant kernel family (the one with the most kernel time in the instrumented
+        # step), e.g. the weight-gradient GEMMs of the VQA answer decoder, not the headline's forward GEMM
+        name, (calls, fms, ffl) = top
+        tf = ffl / (fms * 1e-3) / 1e12 if fms > 0 else 0.0
+        roof = {"bound": "mfma", "kernel": name + " -- the family with the most kernel time in one instrumented step of this workload",
+                "achieved": round(tf, 2), "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / BF16_DENSE_PEAK_TFLOPS, 4),
+                "launches": calls, "avg_launch_us": round(fms / max(calls, 1) * 1e3, 1), "flop_per_launch_avg": ffl / max(calls, 1),
+                "kernel_ms_per_step": round(fms, 3), "traffic": None,
+                "families_ms_per_step": {k: round(v[1], 3) for k, v in sorted(fams.items(), key=lambda kv: -kv[1][1])}}
+    elif dom_n > 0:
+        roof = {"bound": "mfma", "kernel": "gemm_nt_256_kernel<EPI_BF16> (every launch of it in one step: forward / dgrad GEMMs, whole-round parts of tail-split calls included)",
+                "achieved": round(dom_tf, 2), "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": round(dom_tf / BF16_DENSE_PEAK_TFLOPS, 4), "launches": dom_n,
+                "avg_launch_us": round(dom_ms / max(dom_n, 1) * 1e3, 1), "flop_per_launch_avg": dom_fl / max(dom_n, 1),
+                "traffic": traffic, "traffic_note": traffic_note}
+    else:  # no launch of the 256 x 256 kernel at this size: the whole forward / dgrad GEMM family stands in
+        roof = {"bound": "mfma", "kernel": "gemm_nt family (every forward / dgrad GEMM of one step; the 256 x 256 kernel is not selected at these sizes)",
+                "achieved": round(achieved, 2), "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": round(achieved / BF16_DENSE_PEAK_TFLOPS, 4), "launches": nlaunch, "traffic": None}
+    # ... and the whole gemm_nt family (every forward + dgrad GEMM of the step, small tiles included)
+    roof["family_gemm_nt"] = {"achieved": round(achieved, 2), "frac": round(achieved / BF16_DENSE_PEAK_TFLOPS, 4),
+                              "calls": nlaunch, "kernel_ms_per_step": round(gemm_ms, 3), "flop_per_step": gemm_flop}
+    return {
+        # hardware utilisation: 2MNK of every GEMM launched (forward, dgrad, wgrad) + attention, over the timed step
+        "step_tflops_per_gpu_executed": round(step_tf_exec, 2),
+        "mfma_frac_whole_step_executed": round(step_tf_exec / BF16_DENSE_PEAK_TFLOPS, 4),
+        "executed_gflop_per_step": round(executed_flop / 1e9, 1),
+        "roofline": roof,
+    }
+
+
+DUMP_SAMPLE = 4096   # elements per parameter tensor in the dumped samples: 3 float32 arrays, at most 25 MB (VQA: 1047 tensors)
+
+
+def dump_outputs(path, model, optimizer, parts, grad_norm):
+    """What the timed step hands its caller, from its last execution: every loss term and the total gradient norm that
+    optimizer_step returns (float64, shape [1]), and the state the step leaves behind -- the updated parameters and AdamW's two
+    moments -- as a fixed sample (float32): for each stepped parameter in model order, all of it up to DUMP_SAMPLE elements, else
+    DUMP_SAMPLE indices from one CPU generator with a fixed seed, so the indices are the same in every run and build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    scalars = dict(parts)
+    if grad_norm is not None:
+        scalars["grad_norm"] = grad_norm
+    for k, v in scalars.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.asarray([float(v.detach() if torch.is_tensor(v) else v)], dtype=np.float64))
+    optimizer.state_dict()   # (the accelerator publishes its moment arenas as optimizer.state here)
+    g = torch.Generator().manual_seed(20240)
+    cols = {"params": [], "exp_avg": [], "exp_avg_sq": []}
+    for _, p in model.named_parameters():
+        st = optimizer.state.get(p)
+        if not st or "exp_avg" not in st:
+            continue
+        n = p.numel()
+        idx = torch.arange(n) if n <= DUMP_SAMPLE else torch.randint(n, (DUMP_SAMPLE,), generator=g)
+        idx = idx.to(p.device)
+        for key, t in (("params", p.detach()), ("exp_avg", st["exp_avg"]), ("exp_avg_sq", st["exp_avg_sq"])):
+            cols[key].append(t.reshape(-1).index_select(0, idx).float())
+    for key, c in cols.items():
+        if c:
+            np.save(os.path.join(path, f"{key}_sample.npy"), torch.cat(c).cpu().numpy())
+
+
 def main():
     args = parse()
+    # Every reduction of the step in a fixed order (functional.deterministic; the library reads the same variable per call): with the
+    # default float atomics a few small gradient tensors differ in their last bits from run to run and AdamW carries that into every
+    # later step, so two runs with the same arguments would not compute the same thing.  The ordered forms cost ~0.1 ms per step
+    # (DESIGN section 5); XFM_DETERMINISTIC=0 in the environment times the atomic forms.  Set before any rank is started.
+    os.environ.setdefault("XFM_DETERMINISTIC", "1")
     if args.gpus > 1 and "RANK" not in os.environ:
         # invoked bare (`python3 bench.py --gpus N`): start the N ranks ourselves, as the reference's launcher does (run.py:44-75).
         # This parent has made no GPU call (importing torch does not initialise HIP); the ranks are CHILD processes of
@@ -679,6 +820,7 @@ def main():
         os.environ.setdefault("MASTER_PORT", "29671")
         dist.init_process_group(backend, world_size=world, rank=rank)
 
+    from xfm_amd import functional as Fx
     from xfm_amd import marks
     from xfm_amd.accelerators import RCCLDDPAccelerator
 
@@ -694,6 +836,7 @@ def main():
     B = args.batch
     counter = [0]
     comm_events = []
+    grad_norm = [None]   # what optimizer_step returned in the last step (a device tensor: no host sync in the step)
 
     def step(timed_comm=False):
         j = counter[0] % args.pool
@@ -709,7 +852,7 @@ def main():
         if args.no_optimizer:
             model.zero_grad()
         else:
-            acc.optimizer_step(optimizer, model)
+            grad_norm[0] = acc.optimizer_step(optimizer, model)
         marks.mark("step end")
         return parts
 
@@ -737,6 +880,8 @@ def main():
             losses = step(timed_comm=True)
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:   # before any further step changes the model
+            dump_outputs(args.dump_outputs, model, optimizer, losses, grad_norm[0])
         if args.host_time and rank == 0:   # the host's enqueue time of one step with an empty queue in front of it (never waits for a slot)
             hs = []
             for _ in range(8):
@@ -774,88 +919,10 @@ def main():
                 "exposed_comm_note": "HIP events on the launch stream: end of this rank's backward -> its last gradient all-reduce has "
                                      "landed (mean over the timed steps, rank 0); the overlapped part of the exchange ran under backward"}
 
-    # one instrumented step (outside the timed region): HIP events around every gemm_nt launch on the launch stream
-    # (weight-gradient GEMMs normally run on a second stream; for this step they stay on the launch stream so that an event pair
-    # brackets exactly one kernel's execution instead of a stretch of two overlapping chains); the same step counts the MFMA work the
-    # launched kernels execute (2MNK per GEMM + attention)
-    from xfm_amd.xroberta import _WgradStream
-    import xfm_amd.model_pretrain as mp
-    import xfm_amd.xroberta as xr
-    _WgradStream.enabled, text_on, mp._TEXT_STREAM_ON = False, mp._TEXT_STREAM_ON, False  # (the text tower's stream as well)
-    native, xr._NATIVE_LAYERS = xr._NATIVE_LAYERS, False  # kernel by kernel, so that the wrappers see every launch (same kernels)
-    with FlopCounter() as fc:
-        with GemmTimer() as gt:
-            step()
-    _WgradStream.enabled, mp._TEXT_STREAM_ON, xr._NATIVE_LAYERS = os.environ.get("XFM_WGRAD_STREAM", "1") != "0", text_on, native
-    executed_flop = fc.flop
-    nlaunch, gemm_ms, gemm_flop = gt.summary()
-    dom_n, dom_ms, dom_fl, dom_bytes = gt.dominant()
-    dom_tf = dom_fl / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
-    if os.environ.get("XFM_BENCH_GEMM_SHAPES") and rank == 0:
-        with open(os.environ["XFM_BENCH_GEMM_SHAPES"], "w") as f:
-            for (kind, M, N, K, epi), (calls, ms) in sorted(gt.by_shape().items(), key=lambda kv: -kv[1][1]):
-                tf = "" if kind.startswith("attn") else f"{2.0 * M * N * K * calls / ms / 1e9:6.0f}TF"
-                f.write(f"{kind} M={M:6d} N={N:6d} K={K:6d} epi/bias={epi} calls={calls:3d} total={ms:7.3f}ms avg={ms / calls * 1e3:7.1f}us {tf}\n")
-            for n_items, fl, s_, e_ in gt.groups:
-                gms = s_.elapsed_time(e_)
-                f.write(f"tn_group: {n_items} weight gradients in one grouped launch  total={gms:7.3f}ms  {fl / gms / 1e9:6.0f}TF\n")
-    achieved = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
     ms_per_step = elapsed / args.steps * 1e3
-
-    traffic, traffic_note = None, None
-    if pretrain:
-        for name in ("round4_hbm_traffic.json", "round3_hbm_traffic.json", "round2_hbm_traffic.json", "round1_hbm_traffic.json"):
-            tpath = os.path.join(ROOT, "profiles", name)
-            if os.path.exists(tpath):
-                break
-        for name5 in ("round5_hbm_traffic.json",):
-            if os.path.exists(os.path.join(ROOT, "profiles", name5)):
-                name, tpath = name5, os.path.join(ROOT, "profiles", name5)
-        if os.path.exists(tpath):  # PMC passes are separate rocprofv3 runs of this same command (profiles/README.md)
-            with open(tpath) as f:
-                tj = json.load(f)
-            # every instantiation of the plain-bf16 256 x 256 kernel (round 3: <0, persistent?, look-ahead>; before: <0>)
-            dks = [v for k, v in tj["families"].items() if k.startswith("kernel:gemm_nt_256_kernel<0")]
-            dk = {"hbm_bytes_per_step_corrected": sum(v["hbm_bytes_per_step_corrected"] for v in dks),
-                  "launches_per_step": sum(v["launches_per_step"] for v in dks)} if dks else None
-            if dk and dk["launches_per_step"] > 0:  # the dominant kernel's own launches (its average launch, like `achieved`)
-                traffic = dk["hbm_bytes_per_step_corrected"] / dk["launches_per_step"]
-                traffic_note = f"bytes beyond L2 per launch of gemm_nt_256_kernel<0>, averaged over its {dk['launches_per_step']:.0f} launches per step " \
-                               f"(tail-split row blocks included), from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes in profiles/{name} " \
-                               "(2 x FETCH_SIZE + WRITE_SIZE, KB; tools/pmc_traffic.sh); Infinity-Cache hits are counted; algorithmic bytes " \
-                               f"per launch (A + B + C once) average {dom_bytes / max(dom_n, 1):.3e}"
-                prof_hash, tree_hash = tj.get("kernel_tree_hash"), kernel_tree_hash()
-                traffic_note += (f"; profile taken on kernel tree {prof_hash}, this run's tree is {tree_hash}"
-                                 + ("" if prof_hash == tree_hash else " -- the kernels have changed since the profile (or it predates the stamp): "
-                                    "indicative only, re-run tools/pmc_traffic.sh"))
+    full = instrumented_step(step, wl, rank, ms_per_step) if args.full else {}
     if rank == 0:
         gf = wl["gflop"]
-        step_tf_exec = executed_flop / (ms_per_step * 1e-3) / 1e12
-        fams = gt.families()
-        top = max(fams.items(), key=lambda kv: kv[1][1]) if fams else None
-        if not pretrain and top is not None and top[0] != "gemm_nt_256_kernel<EPI_BF16>":
-            # secondary workloads: the roofline is of THEIR dominant kernel family (the one with the most kernel time in the instrumented
-            # step), e.g. the weight-gradient GEMMs of the VQA answer decoder, not the headline's forward GEMM
-            name, (calls, fms, ffl) = top
-            tf = ffl / (fms * 1e-3) / 1e12 if fms > 0 else 0.0
-            roof = {"bound": "mfma", "kernel": name + " -- the family with the most kernel time in one instrumented step of this workload",
-                    "achieved": round(tf, 2), "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / BF16_DENSE_PEAK_TFLOPS, 4),
-                    "launches": calls, "avg_launch_us": round(fms / max(calls, 1) * 1e3, 1), "flop_per_launch_avg": ffl / max(calls, 1),
-                    "kernel_ms_per_step": round(fms, 3), "traffic": None,
-                    "families_ms_per_step": {k: round(v[1], 3) for k, v in sorted(fams.items(), key=lambda kv: -kv[1][1])}}
-        elif dom_n > 0:
-            roof = {"bound": "mfma", "kernel": "gemm_nt_256_kernel<EPI_BF16> (every launch of it in one step: forward / dgrad GEMMs, whole-round parts of tail-split calls included)",
-                    "achieved": round(dom_tf, 2), "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(dom_tf / BF16_DENSE_PEAK_TFLOPS, 4), "launches": dom_n,
-                    "avg_launch_us": round(dom_ms / max(dom_n, 1) * 1e3, 1), "flop_per_launch_avg": dom_fl / max(dom_n, 1),
-                    "traffic": traffic, "traffic_note": traffic_note}
-        else:  # no launch of the 256 x 256 kernel at this size: the whole forward / dgrad GEMM family stands in
-            roof = {"bound": "mfma", "kernel": "gemm_nt family (every forward / dgrad GEMM of one step; the 256 x 256 kernel is not selected at these sizes)",
-                    "achieved": round(achieved, 2), "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(achieved / BF16_DENSE_PEAK_TFLOPS, 4), "launches": nlaunch, "traffic": None}
-        # ... and the whole gemm_nt family (every forward + dgrad GEMM of the step, small tiles included)
-        roof["family_gemm_nt"] = {"achieved": round(achieved, 2), "frac": round(achieved / BF16_DENSE_PEAK_TFLOPS, 4),
-                                  "calls": nlaunch, "kernel_ms_per_step": round(gemm_ms, 3), "flop_per_step": gemm_flop}
         out = {
             "metric": wl["metric"],
             "value": round(B * world * args.steps / elapsed, 2),
@@ -866,24 +933,22 @@ def main():
             "dtype": "bf16", "data": "synthetic",
             "config": dict({"workload": wl["desc"], "units_per_gpu": B, "global_batch": B * world,
                             "dropout": not args.eval_mode, "optimizer_step_in_timed_region": not args.no_optimizer,
+                            "ordered_reductions": Fx.deterministic(),
                             "grad_allreduce": world > 1, "parallelism": f"dp{world}"}, **cfg_extra),
             # throughput credit: the FLOPs the REFERENCE spends on this step over our time -- NOT hardware utilisation
             "step_tflops_per_gpu_reference_count": round(B * gf / ms_per_step, 2) if gf else None,
             "mfma_frac_whole_step": round(B * gf / ms_per_step / BF16_DENSE_PEAK_TFLOPS, 4) if gf else None,
-            # hardware utilisation: 2MNK of every GEMM launched (forward, dgrad, wgrad) + attention, over the timed step
-            "step_tflops_per_gpu_executed": round(step_tf_exec, 2),
-            "mfma_frac_whole_step_executed": round(step_tf_exec / BF16_DENSE_PEAK_TFLOPS, 4),
-            "executed_gflop_per_step": round(executed_flop / 1e9, 1),
             "losses_last_step": loss_vals,
-            "roofline": roof,
         }
+        out.update(full)
         if rccl is not None:
             out["distributed"] = rccl
-        if world == 1 and not forced and not args.no_clocks:
+        alone = args.full and world == 1 and not forced
+        if alone and not args.no_clocks:
             out["clocks_under_load"] = sample_clocks(step)
-        if pretrain and not args.no_fusion_probe and world == 1 and not forced:  # single-rank only: its backward would launch unmatched gradient collectives
+        if alone and pretrain and not args.no_fusion_probe:  # single-rank only: its backward would launch unmatched gradient collectives
             out["fusion_encoder_fwd_bwd"] = fusion_probe(model, B, host[0], packed=not args.padded_rows)
-        if not args.no_cpu_baseline and world == 1 and not forced:  # the CPU baseline is timed at N = 1 only
+        if alone and not args.no_cpu_baseline:  # the CPU baseline is timed at N = 1 only
             out["cpu_baseline"] = cpu_baseline(model, wl, args.cpu_batch or wl["cpu_batch"], args.cpu_threads)
         print(json.dumps(out), flush=True)
     if world > 1 or forced:

@@ -10,10 +10,64 @@ from xfm_amd import synthetic as syn
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 _DT = {"float32": torch.float32, "int64": torch.int64, "int32": torch.int32, "bool": torch.bool}
+# every committed file stays under 1 MiB: a fixture that would be larger is stored as <name>.npz + <name>.part<i>.npz, and the
+# first file's `golden_parts` entry says how many files there are
+PART_BYTES = 900 * 1024
+
+
+def _part_path(name, i, root=GOLDEN):
+    return os.path.join(root, name + (".npz" if i == 0 else f".part{i}.npz"))
+
+
+class Fixture:
+    """The arrays of one fixture across its files: `z[key]`, `key in z`, `z.files` as on a single np.load'ed .npz."""
+
+    def __init__(self, name, root=GOLDEN):
+        first = np.load(_part_path(name, 0, root))
+        n = int(first["golden_parts"]) if "golden_parts" in first.files else 1
+        self._of = {}
+        for z in [first] + [np.load(_part_path(name, i, root)) for i in range(1, n)]:   # a missing part raises
+            for k in z.files:
+                self._of[k] = z
+        self._of.pop("golden_parts", None)
+        self.files = list(self._of)
+
+    def __getitem__(self, key):
+        return self._of[key][key]
+
+    def __contains__(self, key):
+        return key in self._of
+
+
+def save(name, arrays, root=GOLDEN):
+    """Write fixture `name` (key -> array, compressed), split into parts of at most ~PART_BYTES; returns the paths written."""
+    import glob
+    import io
+    import zlib
+    parts, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        buf = io.BytesIO()
+        np.save(buf, np.asarray(v))
+        n = len(zlib.compress(buf.getvalue())) + 2 * len(k) + 160   # deflated payload + zip local / central headers
+        if cur and size + n > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += n
+    parts.append(cur)
+    if len(parts) > 1:
+        parts[0]["golden_parts"] = np.asarray(len(parts))
+    for stale in glob.glob(os.path.join(root, glob.escape(name) + ".part*.npz")):
+        os.remove(stale)
+    paths = []
+    for i, p in enumerate(parts):
+        paths.append(_part_path(name, i, root))
+        np.savez_compressed(paths[-1], **p)
+    return paths
 
 
 def load(name):
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    z = Fixture(name)
     meta = json.loads(str(z["meta"]))
     return z, meta
 

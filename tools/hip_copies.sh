@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 rm -rf /tmp/hiptrace
-cd $R && rocprofv3 --hip-trace --output-format csv -d /tmp/hiptrace -o h -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-fusion-probe > /tmp/hiptrace.log 2>&1
+cd $R && rocprofv3 --hip-trace --output-format csv -d /tmp/hiptrace -o h -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-fusion-probe > /tmp/hiptrace.log 2>&1
 python3 - <<'PY'
 import csv, glob, collections
 f = glob.glob('/tmp/hiptrace/**/h_hip_api_trace.csv', recursive=True)

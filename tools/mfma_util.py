@@ -36,7 +36,7 @@ def main():
                 acc[fam][r["Counter_Name"]] += float(r["Counter_Value"])
                 if r["Counter_Name"] == "GRBM_GUI_ACTIVE":
                     acc[fam]["launches"] += 1
-    out = {"source": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --kernel-trace -- python3 bench.py --steps 2 --warmup 1 "
+    out = {"source": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --kernel-trace -- python3 bench.py --full --steps 2 --warmup 1 "
                      "--no-cpu-baseline --no-fusion-probe with XFM_WGRAD_STREAM=0 XFM_TEXT_STREAM=0 (one kernel at a time)",
            "definition": "mfma_busy_fraction = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 * 1024 SIMDs)", "families": {}}
     for fam, c in sorted(acc.items()):

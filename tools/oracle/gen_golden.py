@@ -96,11 +96,13 @@ class FixedMasks:
 
 
 def save(name, out, meta):
+    """tests/golden_util.save: a fixture over ~900 KiB compressed is split into parts (no committed file over 1 MiB)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import golden_util
     os.makedirs(OUT, exist_ok=True)
     out["meta"] = np.asarray(json.dumps(meta))
-    path = os.path.join(OUT, name + ".npz")
-    np.savez_compressed(path, **out)
-    print(f"wrote {path}: {os.path.getsize(path) / 1024:.0f} KiB", flush=True)
+    for path in golden_util.save(name, out, OUT):
+        print(f"wrote {path}: {os.path.getsize(path) / 1024:.0f} KiB", flush=True)
 
 
 def gen_beit(depth=2, B=4):

@@ -1,10 +1,13 @@
 # rocprofv3 kernel-trace summary of the bench workload with the side streams off (every kernel alone on the GPU: isolated
-# per-kernel durations, the measure of machine work) -> gpurun_out/prof_serial/b_kernel_stats.csv
+# per-kernel durations, the measure of machine work) -> $XFM_PROF_OUT/prof_serial/b_kernel_stats.csv
+R=$(cd "$(dirname "$0")/.." && pwd)
+export XFM_PROF_OUT=${XFM_PROF_OUT:-$R/profile_out}   # where profiles and logs go
+O=$XFM_PROF_OUT
+mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
-rm -rf $R/gpurun_out/prof_serial
+rm -rf $O/prof_serial
 export XFM_WGRAD_STREAM=0 XFM_TEXT_STREAM=0
-cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_serial -o b -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-clocks --no-fusion-probe > gpurun_out/prof_serial.log 2>&1
-find gpurun_out/prof_serial -name "*kernel_trace*" -delete
-tail -1 gpurun_out/prof_serial.log | cut -c1-200
-python3 tools/profile_summary.py gpurun_out/prof_serial/b_kernel_stats.csv 8 60 > gpurun_out/prof_serial_summary.md
+cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_serial -o b -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-clocks --no-fusion-probe > $O/prof_serial.log 2>&1
+find $O/prof_serial -name "*kernel_trace*" -delete
+tail -1 $O/prof_serial.log | cut -c1-200
+python3 tools/profile_summary.py $O/prof_serial/b_kernel_stats.csv 8 60 > $O/prof_serial_summary.md

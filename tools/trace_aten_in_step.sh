@@ -1,11 +1,14 @@
 # The ATen / runtime kernels inside ONE traced training step (the last of the run): count, time, and which of our kernels they sit between.
+R=$(cd "$(dirname "$0")/.." && pwd)
+export XFM_PROF_OUT=${XFM_PROF_OUT:-$R/profile_out}   # where profiles and logs go
+O=$XFM_PROF_OUT
+mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
-rm -rf $R/gpurun_out/ktrace
-cd $R && rocprofv3 --kernel-trace --output-format csv -d gpurun_out/ktrace -o k -- python3 bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-fusion-probe --no-clocks > gpurun_out/ktrace.log 2>&1
+rm -rf $O/ktrace
+cd $R && rocprofv3 --kernel-trace --output-format csv -d $O/ktrace -o k -- python3 bench.py --full --steps 2 --warmup 2 --no-cpu-baseline --no-fusion-probe --no-clocks > $O/ktrace.log 2>&1
 python3 - <<'PY'
-import csv, glob, collections
-f = glob.glob('gpurun_out/ktrace/**/k_kernel_trace.csv', recursive=True)[0]
+import csv, glob, collections, os
+f = glob.glob(os.environ['XFM_PROF_OUT'] + '/ktrace/**/k_kernel_trace.csv', recursive=True)[0]
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r['Start_Timestamp']))
 # the last step = from the last-but-one adamw's end to the last adamw's end
 ad = [i for i, r in enumerate(rows) if 'adamw_kernel' in r['Kernel_Name']]
@@ -23,4 +26,4 @@ print(f"step span {(t1 - t0) / 1e6:.2f} ms, {len(seg)} kernels, of them {sum(cnt
 for k, c in cnt.most_common(25):
     print(f"  {c:4d}  {dur[k] / 1e3:8.1f} us  {k}")
 PY
-rm -rf gpurun_out/ktrace
+rm -rf $O/ktrace

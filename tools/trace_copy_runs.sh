@@ -1,11 +1,14 @@
+R=$(cd "$(dirname "$0")/.." && pwd)
+export XFM_PROF_OUT=${XFM_PROF_OUT:-$R/profile_out}   # where profiles and logs go
+O=$XFM_PROF_OUT
+mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
-rm -rf $R/gpurun_out/ktrace
+rm -rf $O/ktrace
 export XFM_WGRAD_STREAM=0 XFM_TEXT_STREAM=0
-cd $R && rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d gpurun_out/ktrace -o k -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-fusion-probe --no-clocks > gpurun_out/ktrace.log 2>&1
+cd $R && rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/ktrace -o k -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-fusion-probe --no-clocks > $O/ktrace.log 2>&1
 python3 - <<'PY'
-import csv, glob
-f = glob.glob('gpurun_out/ktrace/**/k_kernel_trace.csv', recursive=True)[0]
+import csv, glob, os
+f = glob.glob(os.environ['XFM_PROF_OUT'] + '/ktrace/**/k_kernel_trace.csv', recursive=True)[0]
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r['Start_Timestamp']))
 n = len(rows)
 seg = rows[2 * n // 3:]
@@ -29,11 +32,11 @@ for i in idx:
             shown.add(j)
 for j in sorted(shown):
     print(out[j])
-mc = glob.glob('gpurun_out/ktrace/**/k_memory_copy_trace.csv', recursive=True)
+mc = glob.glob(os.environ['XFM_PROF_OUT'] + '/ktrace/**/k_memory_copy_trace.csv', recursive=True)
 if mc:
     rows = list(csv.DictReader(open(mc[0])))
     import collections
     c = collections.Counter((r.get('Direction'), ) for r in rows)
     print("memory copies in the whole run:", dict(c), "columns", list(rows[0].keys()) if rows else None)
 PY
-rm -rf gpurun_out/ktrace
+rm -rf $O/ktrace
