@@ -1,10 +1,10 @@
 """Where does an entry's time go in the short attention backward's dQ kernel (ViT: 197 x 197, csrc/attention.hip
 attn_bwd_dq_short_kernel)?  Wave 0 of every workgroup stamps nine points of every batch entry it walks (10-ns clock, kernel argument
-`dbg` via XFM_ATTN_DBG_PTR):
+`dbg`, diagnostic library only):
   top | fetched registers + the entry's K / V DMA have landed (vmcnt 0) | barrier 1 passed | next entry's K / V LDS-DMA issued |
   S, dP, exp, delta partial done | barrier 2 passed | dS written to the exchange | barrier 3 passed | dQ summed and stored
 Prints the median / p90 of every phase over all (workgroup, entry) pairs, the entry period, and the kernel time by events.
-Run on the GPU box:  [B=128] python tools/attn_timeline.py"""
+Needs a GPU:  python -m xfm_amd.build --diag && XFM_HIP_LIB=xfm_amd/libxfm_hip_diag.so [B=128] python tools/attn_timeline.py"""
 import os
 import sys
 
@@ -14,6 +14,7 @@ if os.environ.get("LO", "0") == "1":
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from xfm_amd import functional as Fx  # noqa: E402
+from tools import diag_lib  # noqa: E402
 
 
 def main():
@@ -43,14 +44,14 @@ def main():
     torch.cuda.synchronize()
     wave = int(os.environ.get("WAVE", 0))   # which of the 12 waves stamps (wave = 4 * query tile + key range)
     pin = int(os.environ.get("PIN", 0))     # 1: every request of a workgroup goes to its slice's FIRST entry (cache-resident walk; garbage results)
-    assert dbg.data_ptr() % 16 == 0 and 0 <= wave < 8
-    os.environ["XFM_ATTN_DBG_PTR"] = hex(dbg.data_ptr() | wave | (8 if pin else 0))
+    assert 0 <= wave < 8
+    diag_lib.set_timeline(diag_lib.ATTN_SHORT_BWD, dbg, wave | (8 if pin else 0))
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
     bwd()
     e.record()
     torch.cuda.synchronize()
-    os.environ["XFM_ATTN_DBG_PTR"] = ""
+    diag_lib.set_timeline(diag_lib.ATTN_SHORT_BWD, None)
     d = dbg.view(256, 32, 16).cpu()
     d = torch.cat([d[:, :, 0:3], d[:, :, 8:9], d[:, :, 3:8]], dim=2)   # stamp 8 (K / V prefetch issued) sits between 2 and 3
     ok = d[:, :, 8] > 0

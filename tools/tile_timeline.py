@@ -1,13 +1,14 @@
 """Where does a tile's time go in the persistent 256 x 256 NT kernel?  Wave 0 of every workgroup stamps [tile, start, K loop done,
-epilogue done] (10-ns clock) per tile (GemmNT.dbg via XFM_GEMM_DBG_PTR).  Prints, per round, the spread of starts and the medians of
+epilogue done] (10-ns clock) per tile (GemmNT.dbg, diagnostic library only).  Prints, per round, the spread of starts and the medians of
 K-loop time, epilogue time (issue of the stores included, their acknowledgement not), and the gap to the next tile's start.
-Run on the GPU box:  python tools/tile_timeline.py M N K [epi]"""
+Needs a GPU:  python -m xfm_amd.build --diag && XFM_HIP_LIB=xfm_amd/libxfm_hip_diag.so python tools/tile_timeline.py M N K [epi]"""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from xfm_amd import functional as Fx  # noqa: E402
+from tools import diag_lib  # noqa: E402
 
 
 def main():
@@ -22,13 +23,13 @@ def main():
         Fx.gemm_nt(a, b, out=out, bias=bias, epi=epi, aux=aux, tile_hint=5)
     dbg = torch.zeros(256 * 8 * 4, dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
-    os.environ["XFM_GEMM_DBG_PTR"] = hex(dbg.data_ptr())
+    diag_lib.set_timeline(diag_lib.NT_GEMM, dbg)
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
     Fx.gemm_nt(sets[0][0], sets[0][1], out=out, bias=bias, epi=epi, aux=aux, tile_hint=5)
     e.record()
     torch.cuda.synchronize()
-    os.environ["XFM_GEMM_DBG_PTR"] = ""
+    diag_lib.set_timeline(diag_lib.NT_GEMM, None)
     d = dbg.view(256, 8, 4).cpu()
     t0 = int(d[:, 0, 1][d[:, 0, 1] > 0].min())
     print(f"M={M} N={N} K={K} epi={epi}: kernel {s.elapsed_time(e) * 1e3:.1f} us by events; {K // 64} K-steps per tile")

@@ -1,6 +1,5 @@
 """The ViT trunk's grouped weight gradients (48 problems over M = 25216 rows: qkv, proj, fc1, fc2 of 12 blocks) as ONE xfm_gemm_tn_group
-call, as the step launches them: time and TFLOP/s.  XFM_TN_SYNC_WINDOW=<K-steps> turns the XCD progress throttle on (csrc/gemm.hip
-Tn256Seg).  Run on the GPU box: [XFM_TN_SYNC_WINDOW=4] python tools/tn_group_bench.py [blocks=12] [M=25216]"""
+call, as the step launches them: time and TFLOP/s.  Needs a GPU: python tools/tn_group_bench.py [blocks=12] [M=25216]"""
 import os
 import sys
 
@@ -41,7 +40,7 @@ def main():
     for (dy, x, dw, db), _ in zip(items[:4], ref):
         want = 7.0 * (dy.float().t() @ x.float())
         err = max(err, float((dw - want).norm() / want.norm()))
-    print(f"XFM_TN_SYNC_WINDOW={os.environ.get('XFM_TN_SYNC_WINDOW', '0')}: {len(items)} problems, M = {M}: median {ts[2]:.3f} ms (min {ts[0]:.3f}) "
+    print(f"{len(items)} problems, M = {M}: median {ts[2]:.3f} ms (min {ts[0]:.3f}) "
           f"= {flop / ts[2] / 1e9:.0f} TFLOP/s; rel error of dW vs fp32 matmul {err:.2e}")
 
 

@@ -6,6 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libxfm_hip.so")
+DIAG_LIB = os.path.join(HERE, "libxfm_hip_diag.so")   # the same library + the timeline stamps of the tools (-DXFM_DIAG); never loaded by default
 def _sources():
     """Every file the single translation unit (capi.hip) can include: whatever sits in csrc/ plus the public header -- listed from the
     directory, so a new kernel file cannot be forgotten here (round 4: attention_long.hip was, and is_stale() missed edits to it)."""
@@ -45,22 +46,21 @@ def build(force=False, verbose=False):
 _DEVICE_COMPILE = {}
 
 
-def _device_compile():
+def _device_compile(diag=False):
     """One device-only compile to assembly with -Rpass-analysis=kernel-resource-usage (no GPU needed) -> (remarks, assembly text);
-    cached for the process (40 s)."""
-    if "asm" not in _DEVICE_COMPILE:
+    cached for the process (40 s).  diag: the diagnostic library's code (-DXFM_DIAG)."""
+    if diag not in _DEVICE_COMPILE:
         import tempfile
         with tempfile.TemporaryDirectory() as tmp:
             out = os.path.join(tmp, "xfm.s")
-            cmd = [_hipcc()] + FLAGS + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", os.path.join(CSRC, "capi.hip"),
-                                        "-o", out]
+            cmd = [_hipcc()] + FLAGS + (["-DXFM_DIAG"] if diag else []) + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
+                                                                           os.path.join(CSRC, "capi.hip"), "-o", out]
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError("hipcc failed:\n" + r.stdout + r.stderr)
-            _DEVICE_COMPILE["remarks"] = r.stderr
             with open(out) as f:
-                _DEVICE_COMPILE["asm"] = f.read()
-    return _DEVICE_COMPILE["remarks"], _DEVICE_COMPILE["asm"]
+                _DEVICE_COMPILE[diag] = (r.stderr, f.read())
+    return _DEVICE_COMPILE[diag]
 
 
 def resource_usage():
@@ -103,5 +103,20 @@ def kernel_isa():
     return out
 
 
+def build_diag(verbose=False):
+    """The diagnostic library: same flags plus -DXFM_DIAG (wall-clock stamps in two kernels + xfm_diag_set_timeline).  The tools that
+    want it load it through XFM_HIP_LIB."""
+    cmd = [_hipcc()] + FLAGS + ["-DXFM_DIAG", "-shared", os.path.join(CSRC, "capi.hip"), "-o", DIAG_LIB]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed:\n" + r.stdout + r.stderr)
+    return DIAG_LIB
+
+
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True))
+    if "--diag" in sys.argv:
+        print(build_diag(verbose=True))
+    else:
+        print(build(force="--force" in sys.argv, verbose=True))

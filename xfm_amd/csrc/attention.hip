@@ -11,7 +11,6 @@
 // projection GEMM buffers ([B*S, 3*768] for self-attention, [B*Sk, 2*768] for the cross-attention K/V).
 #include <type_traits>
 #include "common.h"
-#include <stdlib.h>
 
 #define MASK_NEG (-10000.0f)
 #define EXCL_NEG (-1.0e30f)
@@ -587,8 +586,15 @@ __device__ __forceinline__ void lds_barrier() {
 // PRE: the row term delta_i = dO_i . (O_i + Olo_i) is taken from the forward's output (a.o, a.o_lo) at the top of an entry, from
 // fragments fetched one entry ahead -- no delta exchange, no second barrier, and dS leaves in the same phase as the scores.
 // !PRE (no o_lo): delta_i = sum_j P_ij dP_ij from the very P and dP that form dS, exchanged between the four key-range waves.
-template <int QT, int NP, bool PRE, bool DBG>
+#ifdef XFM_DIAG
+// DBG: the stamped build (tools/attn_timeline.py).  dbg = the timeline buffer, 16-byte aligned, with xfm_diag_set_timeline's flags in
+// its low bits: the stamping wave (0..7) | 8 = pin mode
+template <int QT, int NP, bool PRE, bool DBG = false>
 __global__ __launch_bounds__(QT * 256) void attn_bwd_dq_short_kernel(AttnArgs a, int nb_per_block, int G, long long* dbg) {
+#else
+template <int QT, int NP, bool PRE>
+__global__ __launch_bounds__(QT * 256) void attn_bwd_dq_short_kernel(AttnArgs a, int nb_per_block, int G) {
+#endif
   constexpr int NW = QT * 4;
   // QL (PRE and <= 14 key tiles): the Q / dO tiles of the workgroup's queries come through LDS too -- 4 QT one-KB pieces per entry instead
   // of four fragment loads in each of the 4 QT waves (every key-range wave of a query tile fetched the same rows) -- in the room
@@ -683,11 +689,15 @@ __global__ __launch_bounds__(QT * 256) void attn_bwd_dq_short_kernel(AttnArgs a,
   const float* plse = a.lse + (long)b_begin * stat_bs;
   float* pdelta = a.delta + (long)b_begin * stat_bs;
   char* pdq = reinterpret_cast<char*>(a.dq) + (long)(b_begin - 1) * dq_bs;
-  // (diagnostic build only: bit 3 of the pointer's low bits pins every request on the slice's first entry -- the whole walk then runs
-  // from cache, which prices the memory side of the entry period; results are garbage)
+#ifdef XFM_DIAG
+  // pin mode: every request stays on the slice's first entry -- the whole walk then runs from cache, which prices the memory side of
+  // the entry period; results are garbage
   const bool pin = DBG && ((uintptr_t)dbg & 8) != 0;
+#endif
   auto advance = [&]() {
-    if (DBG && pin) return;
+#ifdef XFM_DIAG
+    if (pin) return;
+#endif
     pk += k_bs; pv += v_bs; pq += q_bs; pdo += do_bs; plse += stat_bs;
     if constexpr (PRE) { po += o_bs; plo += o_bs; }
   };
@@ -790,8 +800,10 @@ __global__ __launch_bounds__(QT * 256) void attn_bwd_dq_short_kernel(AttnArgs a,
     fetch_q(b_begin);
     advance();
   }
-  const int dbg_wave = (int)((uintptr_t)dbg & 7);   // (the stamping wave, 0..7, rides in the low bits of the 256-B aligned diagnostic pointer)
+#ifdef XFM_DIAG
+  const int dbg_wave = (int)((uintptr_t)dbg & 7);
   dbg = reinterpret_cast<long long*>((uintptr_t)dbg & ~(uintptr_t)15);
+#endif
   // The number of key tiles of a wave (nt, 0..4) is a run-time, wave-uniform value.  Written as `if (t < nt)` inside the tile loops it
   // made every tile its own exec-masked basic block -- read, wait, MFMA, read, wait, MFMA: 16 LDS round trips in series.  So the whole
   // walk is straight-line code per tile COUNT (NT; -1 = a wave without a query tile: barriers and its share of the staging only),
@@ -804,9 +816,11 @@ __global__ __launch_bounds__(QT * 256) void attn_bwd_dq_short_kernel(AttnArgs a,
     for (int b = b_begin; b < b_end; ++b) {
       const int cur = (b - b_begin) & 1;
       const char* sK = sK0 + cur * KBUF;
-      // diagnostic (XFM_ATTN_DBG_PTR, tools/attn_timeline.py): one wave stamps the phases of every entry (10-ns clock); NULL in every product call
+#ifdef XFM_DIAG
+      // one wave stamps the phases of every entry (10-ns clock)
       long long* const dbe = DBG && dbg != nullptr && tid == dbg_wave * 64 && b - b_begin < 32 ? dbg + ((long)blockIdx.x * 32 + (b - b_begin)) * 16 : nullptr;
       if (DBG && dbe) dbe[0] = wall_clock64();
+#endif
       // everything up to the fetches of this entry must have landed.  (The compiler cannot see this wait: the empty asm makes it place
       // its own wait for the fetched registers HERE, before this entry's direct-to-LDS loads are issued, rather than at their first
       // use, where a counted wait would also drain those.)
@@ -840,9 +854,13 @@ __global__ __launch_bounds__(QT * 256) void attn_bwd_dq_short_kernel(AttnArgs a,
         const float part = group4_sum(t0 + t1);
         if (lg == 0) dred[(qt * 16 + lr) * 4 + kw] = part;
       }
+#ifdef XFM_DIAG
       if (DBG && dbe) dbe[1] = wall_clock64();
+#endif
       lds_barrier();  // K(b), V(b) have landed; every wave is done with entry b-1 (its K / V buffers, the exchange tiles)
+#ifdef XFM_DIAG
       if (DBG && dbe) dbe[2] = wall_clock64();
+#endif
       if constexpr (PRE && ACT) {
         const f32x4 dq4 = *reinterpret_cast<const f32x4*>(dred + (qt * 16 + lr) * 4);
         delta = (dq4[0] + dq4[1]) + (dq4[2] + dq4[3]);
@@ -867,7 +885,9 @@ __global__ __launch_bounds__(QT * 256) void attn_bwd_dq_short_kernel(AttnArgs a,
       // (placing the K / V pieces between the tiles of the score phase instead -- one K + V piece per tile -- measured the same entry period
       // with ~50 more scalar instructions per entry; all of them go out here)
       if (more) stage_kv(b + 1, cur ^ 1);
+#ifdef XFM_DIAG
       if (DBG && dbe) dbe[8] = wall_clock64();
+#endif
 
       f32x4 st[NTS], dp[NTS];
       if constexpr (ACT) {
@@ -955,11 +975,15 @@ __global__ __launch_bounds__(QT * 256) void attn_bwd_dq_short_kernel(AttnArgs a,
           if (lg == 0) dred[(qt * 4 + kw) * 16 + lr] = dpart;
         }
       }
+#ifdef XFM_DIAG
       if (DBG && dbe) dbe[3] = wall_clock64();
+#endif
       if constexpr (!QL) if (more) fetch_q(b + 1);  // (here, not at the top: this entry's fragments are dead now and lend their registers)
       if constexpr (!PRE) {
         lds_barrier();  // delta partials are in
+#ifdef XFM_DIAG
         if (DBG && dbe) dbe[4] = wall_clock64();
+#endif
         if constexpr (ACT) {
           // delta_i = sum_j P_ij dP_ij from the SAME P and dP that form dS, so that sum_j dS_ij = 0 holds to fp32 rounding
           delta = (dred[(qt * 4 + 0) * 16 + lr] + dred[(qt * 4 + 1) * 16 + lr]) + (dred[(qt * 4 + 2) * 16 + lr] + dred[(qt * 4 + 3) * 16 + lr]);
@@ -976,10 +1000,15 @@ __global__ __launch_bounds__(QT * 256) void attn_bwd_dq_short_kernel(AttnArgs a,
             *reinterpret_cast<bf16x4*>(ex_slot(kt0 + t)) = pk;
           }
         }
-      } else if (DBG && dbe) dbe[4] = wall_clock64();
+      }
+#ifdef XFM_DIAG
+      if (PRE && DBG && dbe) dbe[4] = wall_clock64();
       if (DBG && dbe) dbe[5] = wall_clock64();
+#endif
       lds_barrier();  // the query tile's dS tiles of all keys are in
+#ifdef XFM_DIAG
       if (DBG && dbe) dbe[6] = wall_clock64();
+#endif
       if constexpr (ACT) {
         // dQ^T[d, q] = sum_keys K^T[d, key] dS^T[key, q] for d-tile kw, two key tiles per MFMA.  Straight-line over NP pairs (tiles past
         // the last one hold zeros) so that the LDS reads of several pairs are in flight together; two chains of dependent MFMAs.
@@ -998,7 +1027,9 @@ __global__ __launch_bounds__(QT * 256) void attn_bwd_dq_short_kernel(AttnArgs a,
 #pragma unroll
         for (int r = 0; r < 4; ++r) dq_hold[r] = f2bf(acc[r] * a.scale);
       }
+#ifdef XFM_DIAG
       if (DBG && dbe) dbe[7] = wall_clock64();
+#endif
       advance();
       pdelta += stat_bs;
       pdq += dq_bs;
@@ -2129,7 +2160,7 @@ static void attn_geom(int S, int& nw, int& blocks, int max_nw = 8) {
 // packed or not (they are bound by each wave's dependent load -> MFMA -> exp -> MFMA chain, not by occupancy) and stay
 // one row per workgroup.  XFM_ATTN_PACK=0 is the A/B knob.
 static bool attn_packable(const AttnArgs& a) {
-  static const bool on = getenv("XFM_ATTN_PACK") ? atoi(getenv("XFM_ATTN_PACK")) != 0 : true;
+  static const bool on = xfm_env_flag("XFM_ATTN_PACK", true);
   return on && a.Sq <= 64 && a.Sk <= 64 && a.bias == nullptr && a.bias_t == nullptr && a.B >= 2;
 }
 
@@ -2192,7 +2223,7 @@ int xfm_attn_fwd_impl(const AttnArgs& a, hipStream_t st) {
   }
   if (attn_vit_shape(a)) return launch_attn_fwd_vit(a, st);
   int nw, blocks;
-  static const int fwd_nw = getenv("XFM_ATTN_FWD_NW") ? atoi(getenv("XFM_ATTN_FWD_NW")) : 8;  // tuning knob
+  static const int fwd_nw = xfm_env_int("XFM_ATTN_FWD_NW", 8);  // tuning knob
   attn_geom(a.Sq, nw, blocks, fwd_nw);
   const dim3 grid(blocks, a.H, a.B), blk(nw * 64);
   const size_t lds = attn_lds_bytes(a.Sk, nw, 0);
@@ -2217,7 +2248,7 @@ __global__ __launch_bounds__(256) void dbias_reduce_kernel(const float* __restri
 
 // the short dense backward pair (attn_bwd_dq_short_kernel / attn_bwd_dkv_short_kernel) takes this problem
 static bool attn_short_dq_ok(const AttnArgs& a) {
-  static const bool short_env = getenv("XFM_ATTN_SHORT_BWD") ? atoi(getenv("XFM_ATTN_SHORT_BWD")) != 0 : true;  // A/B knob
+  static const bool short_env = xfm_env_flag("XFM_ATTN_SHORT_BWD", true);  // A/B knob
   return short_env && attn_plain(a) && a.Sk <= 64 * ATTN_RES_MAX && a.q_start == nullptr && a.k_start == nullptr && a.kv_index == nullptr &&
          (a.bias == nullptr || a.bias_ld >= (long)cdiv(a.Sk, 16) * 16) && (a.dbias == nullptr || a.bias_ld >= a.Sk);
 }
@@ -2232,10 +2263,7 @@ static int attn_short_dq_slices(const AttnArgs& a, int& groups, int& nb) {
 // XFM_DETERMINISTIC=1: the reductions that still end in float atomics by default because the ordered form costs a launch or a pass
 // (the bias gradient of the short attention backward: one plane per batch slice + dbias_reduce_kernel; the embedding gradients) take
 // the ordered form.  Read per call.
-static bool xfm_deterministic() {
-  const char* e = getenv("XFM_DETERMINISTIC");
-  return e != nullptr && atoi(e) != 0;
-}
+static bool xfm_deterministic() { return xfm_env_flag("XFM_DETERMINISTIC", false); }
 // planes for the short dQ kernel's bias gradient: deterministic mode, more than one batch slice, and rows it can cover completely
 static bool attn_short_dbias_planes(const AttnArgs& a) {
   int groups, nb;
@@ -2243,6 +2271,11 @@ static bool attn_short_dbias_planes(const AttnArgs& a) {
          attn_short_dq_slices(a, groups, nb) > 1;
 }
 #include "attention_long.hip"
+
+#ifdef XFM_DIAG
+// Diagnostic build: where the next launches of attn_bwd_dq_short_kernel put their stamps (xfm_diag_set_timeline, capi.hip); ptr NULL = off
+static XfmTimeline attn_short_timeline = {nullptr, 0, 0};
+#endif
 
 int xfm_attn_bwd_impl(const AttnArgs& a_in, hipStream_t st) {
   AttnArgs a = a_in;
@@ -2269,7 +2302,7 @@ int xfm_attn_bwd_impl(const AttnArgs& a_in, hipStream_t st) {
       if (rc != XFM_OK || a.bwd_phase == 1) return rc;
     }
     int knw, kblocks;
-    static const int dkv_nw = getenv("XFM_XATTN_DKV_NW") ? atoi(getenv("XFM_XATTN_DKV_NW")) : 16;  // tuning knob: waves (16-key tiles) per workgroup
+    static const int dkv_nw = xfm_env_int("XFM_XATTN_DKV_NW", 16);  // tuning knob: waves (16-key tiles) per workgroup
     attn_geom(a.Sk, knw, kblocks, dkv_nw);
     const size_t dkv_lds = (size_t)ATTN_RES_MAX * ATTN_SLOT + 3 * ATTN_RES_MAX * 64 * 4;
     if (a.drop_thresh != 0u) hipLaunchKernelGGL(xattn_dkv_kernel<true>, dim3(kblocks, a.H, a.n_groups), dim3(knw * 64), dkv_lds, st, a);
@@ -2310,15 +2343,17 @@ int xfm_attn_bwd_impl(const AttnArgs& a_in, hipStream_t st) {
   if (a.bwd_phase == 2) {
     // dK/dV alone: `delta` was written by an earlier phase-1 call
   } else if (short_dq) {
+#define XFM_DQS_BYTES(NP, PRE) ((PRE) && (NP) <= 7 ? VB_LDS_QL(3, NP) : VB_LDS(3))
     static bool attr_set = false;
     if (!attr_set) {
-#define XFM_DQS_BYTES(NP, PRE) ((PRE) && (NP) <= 7 ? VB_LDS_QL(3, NP) : VB_LDS(3))
-#define XFM_DQS_ATTR(NP, PRE) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_short_kernel<3, NP, PRE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, XFM_DQS_BYTES(NP, PRE))
+#define XFM_DQS_ATTR(NP, PRE) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_short_kernel<3, NP, PRE>), hipFuncAttributeMaxDynamicSharedMemorySize, XFM_DQS_BYTES(NP, PRE))
       XFM_DQS_ATTR(4, false); XFM_DQS_ATTR(7, false); XFM_DQS_ATTR(8, false);
       XFM_DQS_ATTR(4, true); XFM_DQS_ATTR(7, true); XFM_DQS_ATTR(8, true);
+#undef XFM_DQS_ATTR
+#ifdef XFM_DIAG
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_short_kernel<3, 7, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, XFM_DQS_BYTES(7, false));
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_short_kernel<3, 7, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, XFM_DQS_BYTES(7, true));
-#undef XFM_DQS_ATTR
+#endif
       attr_set = true;
     }
     // (query groups x heads) workgroups per batch slice; slices so that one round of <= 256 workgroups covers the batch
@@ -2327,29 +2362,40 @@ int xfm_attn_bwd_impl(const AttnArgs& a_in, hipStream_t st) {
     const int slices = attn_short_dq_slices(a, groups, nb);
     const dim3 grid(groups * a.H * slices);
     a.dbias_ws = short_planes;   // (NULL: float atomics into dbias)
-    long long* dbg = nullptr;
-    {
-      const char* dp = getenv("XFM_ATTN_DBG_PTR");   // (read per launch: tools/attn_timeline.py sets it around the one call it wants a timeline of)
-      if (dp != nullptr && dp[0] != 0) dbg = reinterpret_cast<long long*>(strtoull(dp, nullptr, 0));   // (| stamping wave, 0..11)
-    }
     // NP = key-tile pairs the dQ loop runs over.  XFM_ATTN_SHORT_PRE=1 (opt-in): the row term delta from dO . (O + O_lo) when the forward
     // kept the low half of O -- one barrier and the delta exchange less per entry, Q / dO through LDS, and MEASURED SLOWER (dQ 121 us
     // against 97.5 at B = 128, 197 tokens: profiles/round5_attn_short.md), so the exchange form stays the default
-    const char* pe = getenv("XFM_ATTN_SHORT_PRE");   // (read per call: the tests switch it inside one process)
-    const bool pre_env = pe != nullptr && atoi(pe) != 0;
+    const bool pre_env = xfm_env_flag("XFM_ATTN_SHORT_PRE", false);   // (read per call: the tests switch it inside one process)
     const bool pre = pre_env && a.o != nullptr && a.o_lo != nullptr;
-#define XFM_DQS_LAUNCH(NP)                                                                                                      \
-  do {                                                                                                                          \
-    if (pre) hipLaunchKernelGGL((attn_bwd_dq_short_kernel<3, NP, true, false>), grid, dim3(768), XFM_DQS_BYTES(NP, true), st, a, nb, groups, dbg);    \
-    else hipLaunchKernelGGL((attn_bwd_dq_short_kernel<3, NP, false, false>), grid, dim3(768), XFM_DQS_BYTES(NP, false), st, a, nb, groups, dbg);      \
+#ifdef XFM_DIAG
+    // the stamped build exists for the ViT shape only (tools/attn_timeline.py); every other launch of a diagnostic library goes unstamped
+    long long* dbg = a.Sk > 128 && a.Sk <= 224 ? attn_short_timeline.ptr : nullptr;
+    if (dbg != nullptr && attn_short_timeline.bytes < (size_t)grid.x * XFM_ATTN_SHORT_STAMP_BYTES) {
+      xfm_set_error("attn_bwd_dq_short: timeline buffer of %zu bytes is short of %u workgroups x %d: launched without stamps",
+                    attn_short_timeline.bytes, grid.x, XFM_ATTN_SHORT_STAMP_BYTES);
+      dbg = nullptr;
+    }
+    if (dbg != nullptr) dbg = reinterpret_cast<long long*>((uintptr_t)dbg | (uintptr_t)(attn_short_timeline.flags & 15));
+#define XFM_DQS_ARGS a, nb, groups, nullptr   // (the unstamped instantiations ignore their timeline argument)
+#else
+#define XFM_DQS_ARGS a, nb, groups
+#endif
+#define XFM_DQS_LAUNCH(NP)                                                                                             \
+  do {                                                                                                                 \
+    if (pre) hipLaunchKernelGGL((attn_bwd_dq_short_kernel<3, NP, true>), grid, dim3(768), XFM_DQS_BYTES(NP, true), st, XFM_DQS_ARGS);    \
+    else hipLaunchKernelGGL((attn_bwd_dq_short_kernel<3, NP, false>), grid, dim3(768), XFM_DQS_BYTES(NP, false), st, XFM_DQS_ARGS);      \
   } while (0)
-    if (dbg != nullptr && a.Sk > 128 && a.Sk <= 224) {   // the stamped build exists for the ViT shape only (tools/attn_timeline.py)
+#ifdef XFM_DIAG
+    if (dbg != nullptr) {
       if (pre) hipLaunchKernelGGL((attn_bwd_dq_short_kernel<3, 7, true, true>), grid, dim3(768), XFM_DQS_BYTES(7, true), st, a, nb, groups, dbg);
       else hipLaunchKernelGGL((attn_bwd_dq_short_kernel<3, 7, false, true>), grid, dim3(768), XFM_DQS_BYTES(7, false), st, a, nb, groups, dbg);
-    } else if (a.Sk <= 128) XFM_DQS_LAUNCH(4);
+    } else
+#endif
+    if (a.Sk <= 128) XFM_DQS_LAUNCH(4);
     else if (a.Sk <= 224) XFM_DQS_LAUNCH(7);
     else XFM_DQS_LAUNCH(8);
 #undef XFM_DQS_LAUNCH
+#undef XFM_DQS_ARGS
   } else if (a.dbias != nullptr && res && plain) {
     // batch entries whose dS one workgroup sums before touching HBM.  The kernel holds 230+ VGPRs (sum_b dS of four chunks), i.e.
     // one workgroup per CU: of 4 and 8 entries take the one with fewer (rounds of 256 workgroups) x entries, ties to 8
@@ -2359,7 +2405,7 @@ int xfm_attn_bwd_impl(const AttnArgs& a_in, hipStream_t st) {
       const long c4 = (long)cdiv(blocks * a.H * cdiv(a.B, 4), 256) * 4, c8 = (long)cdiv(blocks * a.H * cdiv(a.B, 8), 256) * 8;
       nb = c8 <= c4 ? 8 : 4;
     }
-    static const int nb_env = getenv("XFM_ATTN_DBIAS_NB") ? atoi(getenv("XFM_ATTN_DBIAS_NB")) : 0;  // tuning knob
+    static const int nb_env = xfm_env_int("XFM_ATTN_DBIAS_NB", 0);  // tuning knob
     if (nb_env > 0) nb = nb_env;
     hipLaunchKernelGGL((attn_bwd_dq_kernel<4, true, true>), dim3(blocks, a.H, cdiv(a.B, nb)), dim3(nw * 64),
                        attn_lds_bytes(a.Sk, nw, 8 * 4096), st, a, nb);
@@ -2405,7 +2451,7 @@ int xfm_attn_bwd_impl(const AttnArgs& a_in, hipStream_t st) {
   }
   attn_geom(a.Sk, nw, blocks);
   const dim3 grid(blocks, a.H, a.B), blk(nw * 64);
-  static const bool dkv_res = getenv("XFM_ATTN_DKV_RES") ? atoi(getenv("XFM_ATTN_DKV_RES")) != 0 : true;  // tuning knob
+  static const bool dkv_res = xfm_env_flag("XFM_ATTN_DKV_RES", true);  // tuning knob
   if (dkv_res && attn_resident(a.Sq, nw)) {
     if (plain) hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, true>), grid, blk, attn_lds_bytes(a.Sq, nw, 0), st, a);
     else hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, false>), grid, blk, attn_lds_bytes(a.Sq, nw, 0), st, a);

@@ -586,7 +586,7 @@ static int dbias_long_slices(int blocks, int B, long plane_bytes) {
 }
 
 static bool attn_long_shape(const AttnArgs& a) {
-  static const bool on = getenv("XFM_ATTN_LONG") ? atoi(getenv("XFM_ATTN_LONG")) != 0 : true;  // A/B knob: 0 = the general kernels
+  static const bool on = xfm_env_flag("XFM_ATTN_LONG", true);  // A/B knob: 0 = the general kernels
   return on && a.Sk > 64 * ATTN_RES_MAX && a.key_keep == nullptr && a.causal == 0 && a.drop_thresh == 0u && a.q_start == nullptr &&
          a.k_start == nullptr && a.kv_index == nullptr && a.grp_start == nullptr &&
          (a.bias == nullptr || (a.bias_ld % 4 == 0 && a.bias_ld >= (long)cdiv(a.Sk, 4) * 4 && ((uintptr_t)a.bias % 16) == 0)) &&
@@ -597,8 +597,7 @@ static bool attn_long_shape(const AttnArgs& a) {
 // XFM_ATTN_VIT_BWD=4 (experiment): the single-pass backward WITHOUT its bias-gradient sums (they are what spills it) + this file's
 // block-walking bias-gradient kernel on the delta it wrote
 static bool attn_vit_split_dbias(const AttnArgs& a) {
-  const char* e = getenv("XFM_ATTN_VIT_BWD");
-  return e != nullptr && atoi(e) == 4 && a.dbias != nullptr && attn_vit3_shape(a) && a.bias_ld % 4 == 0 && a.bias_ld <= (long)cdiv(a.Sk, 128) * 128 &&
+  return xfm_env_int("XFM_ATTN_VIT_BWD", 0) == 4 && a.dbias != nullptr && attn_vit3_shape(a) && a.bias_ld % 4 == 0 && a.bias_ld <= (long)cdiv(a.Sk, 128) * 128 &&
          ((uintptr_t)a.dbias % 16) == 0 && ((uintptr_t)a.bias % 16) == 0;
 }
 long xfm_attn_bwd_workspace_impl(const AttnArgs& a) {

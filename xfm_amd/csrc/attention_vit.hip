@@ -44,7 +44,7 @@ static VitMap vit_map(int B, int H) {
   m.slices = 256 / H > 0 ? 256 / H : 1;
   // default: head-major flat ranges (measured: the slice-synchronous map is no faster for the forward -- 61.0 vs 58.9 us -- and its
   // leftover workgroups, with several heads each, flush the backward's bias gradient several times: 316 vs 271 us)
-  static const int flat = getenv("XFM_ATTN_VIT_FLAT") ? atoi(getenv("XFM_ATTN_VIT_FLAT")) : 1;
+  static const int flat = xfm_env_int("XFM_ATTN_VIT_FLAT", 1);
   m.c = B / m.slices;
   if (m.c == 0 || flat) {   // fewer entries than slices: one entry per slice
     m.slices = flat ? 0 : B;
@@ -268,7 +268,7 @@ int xfm_bias_tile_impl(const float* bias, int H, int S, long ld, float scale, fl
 }
 
 static bool attn_vit_shape(const AttnArgs& a) {
-  static const bool on = getenv("XFM_ATTN_VIT") ? atoi(getenv("XFM_ATTN_VIT")) != 0 : true;  // A/B knob: 0 = the general kernels
+  static const bool on = xfm_env_flag("XFM_ATTN_VIT", true);  // A/B knob: 0 = the general kernels
   return on && a.Sq == a.Sk && a.Sq > 64 && a.Sq <= 16 * VF_MAXT && a.key_keep == nullptr && a.causal == 0 && a.drop_thresh == 0u &&
          a.q_start == nullptr && a.k_start == nullptr && a.kv_index == nullptr && a.grp_start == nullptr &&
          (a.bias == nullptr || (a.bias_ld >= (long)cdiv(a.Sk, 16) * 16 && a.bias_ld % 4 == 0)) &&  // (untiled bias rows are read 16 B at a time)
@@ -661,8 +661,7 @@ __global__ __launch_bounds__(512) void attn_bwd_vit3_kernel(AttnArgs a, VitMap v
 }
 
 static bool attn_vit3_shape(const AttnArgs& a) {
-  const char* e = getenv("XFM_ATTN_VIT_BWD");   // (read per call: the tests switch it inside one process)
-  const int mode = e != nullptr ? atoi(e) : 0;
+  const int mode = xfm_env_int("XFM_ATTN_VIT_BWD", 0);   // (read per call: the tests switch it inside one process)
   return mode != 0 && attn_vit_shape(a) && cdiv(a.Sq, 16) == V3_KT && a.bwd_phase == 0 && a.o != nullptr && a.o_lo == nullptr &&
          (a.bias == nullptr || a.bias_t_tiled != nullptr) && (a.dbias == nullptr || a.bias != nullptr) &&
          ((uintptr_t)a.dout % 16) == 0 && ((uintptr_t)a.o % 16) == 0 && a.o_rs % 8 == 0;

@@ -295,4 +295,34 @@ int xfm_dp_broadcast(void* comm, void* buf, long n, int dtype, int root, void* s
 }
 int xfm_dp_finalize(void* comm) { return xfm_dp_finalize_impl(comm); }
 
+#ifdef XFM_DIAG
+// Diagnostic build only (python -m xfm_amd.build --diag; not part of the ABI of include/xfm_hip.h): the launches that follow of
+// which = 0: gemm_nt_256_kernel (tools/tile_timeline.py; flags unused), which = 1: attn_bwd_dq_short_kernel at 129..224 keys
+// (tools/attn_timeline.py; flags = the stamping wave 0..7 | 8 = pin mode, whose results are garbage) write their stamps to ptr[0 .. bytes).
+// ptr: 16-byte aligned device memory of the current device (NULL = stamps off).  A launch whose grid needs more than `bytes` goes
+// unstamped and leaves an error string.
+int xfm_diag_set_timeline(int which, void* ptr, size_t bytes, int flags) {
+  XFM_REQUIRE(which == 0 || which == 1, "diag_set_timeline: which = %d (0: NT GEMM, 1: short attention backward)", which);
+  XfmTimeline& t = which == 0 ? nt256_timeline : attn_short_timeline;
+  if (ptr == nullptr) {
+    t = XfmTimeline{nullptr, 0, 0};
+    return XFM_OK;
+  }
+  XFM_REQUIRE(flags >= 0 && flags < (which == 0 ? 1 : 16), "diag_set_timeline: bad flags %d", flags);
+  XFM_REQUIRE(((uintptr_t)ptr % 16) == 0, "diag_set_timeline: the buffer must be 16-byte aligned");
+  XFM_REQUIRE(bytes >= (size_t)(which == 0 ? XFM_NT256_STAMP_BYTES : XFM_ATTN_SHORT_STAMP_BYTES),
+              "diag_set_timeline: %zu bytes hold not even one workgroup's stamps", bytes);
+  int dev = -1;
+  hipPointerAttribute_t at;
+  if (hipGetDevice(&dev) != hipSuccess || hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+    (void)hipGetLastError();
+    xfm_set_error("diag_set_timeline: %p is not a pointer the runtime knows", ptr);
+    return XFM_E_ARG;
+  }
+  XFM_REQUIRE(at.type == hipMemoryTypeDevice && at.device == dev, "diag_set_timeline: %p is not device memory of the current device", ptr);
+  t = XfmTimeline{reinterpret_cast<long long*>(ptr), bytes, flags};
+  return XFM_OK;
+}
+#endif
+
 }  // extern "C"

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -32,6 +33,22 @@ int xfm_cu_count();
   } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// The one reader of the library's environment knobs (every name is listed in tools/README.md).  Callers keep the value in a
+// `static const` unless a test flips the variable inside one process.
+static inline int xfm_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e != nullptr ? atoi(e) : dflt;
+}
+static inline bool xfm_env_flag(const char* name, bool dflt) { return xfm_env_int(name, dflt ? 1 : 0) != 0; }
+
+#ifdef XFM_DIAG
+// Diagnostic build only (python -m xfm_amd.build --diag): the device buffer that the stamped kernels write their 10-ns wall-clock stamps
+// to, set by xfm_diag_set_timeline (capi.hip), and the bytes ONE workgroup of each stamped kernel writes to it.
+struct XfmTimeline { long long* ptr; size_t bytes; int flags; };
+constexpr int XFM_NT256_STAMP_BYTES = 8 * 4 * 8;       // gemm_nt_256_kernel: 8 tiles x [tile, start, K loop done, epilogue done]
+constexpr int XFM_ATTN_SHORT_STAMP_BYTES = 32 * 16 * 8;  // attn_bwd_dq_short_kernel: 32 batch entries x 16 slots (9 used)
+#endif
 
 #ifdef __HIPCC__
 // ---------------------------------------------------------------------------------------------

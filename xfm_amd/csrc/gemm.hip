@@ -11,7 +11,6 @@
 // C^T tiles (A-operand = weight rows, B-operand = activation rows) so that after the K loop every lane owns 8
 // CONSECUTIVE output columns of one output row: bias/GELU are applied in registers and the row is stored 16 B per lane.
 #include "common.h"
-#include <stdlib.h>
 
 enum { EPI_BF16 = 0, EPI_F32 = 1, EPI_GELU = 2, EPI_DGELU = 3, EPI_F32_ACC = 4 };
 
@@ -34,12 +33,11 @@ struct GemmNT {
   int M, N, K;
   int group_m;  // row-panels per tile group (L2 locality of the block order)
   int k_splits; // small-tile kernels, EPI_F32_ACC only: gridDim.y K-slices, fp32 atomics into C (1 = off)
-  int k_rot;    // 256 x 256 kernel: column phases of the K rotation (0 / 1 = every tile starts at K-tile 0)
   long split_stride;  // EPI_F32 with k_splits > 1: K-slice y stores its partial tile to C + y * split_stride (elements), plain stores
-  int skew_from, skew_ticks;  // persistent 256 x 256 kernel: workgroup i >= skew_from starts (i - skew_from) / (grid - skew_from) * skew_ticks
-                              // later (10-ns ticks of the constant clock); 0 = all at once.  See launch_nt_256.
-  long long* dbg;             // diagnostic (XFM_GEMM_DBG_PTR, tools/tile_timeline.py): wave 0 of every workgroup writes 10-ns timestamps
-                              // [tile index, start, K loop done, epilogue done] per tile it walks; NULL in every product call
+#ifdef XFM_DIAG
+  long long* dbg;  // 256 x 256 kernel (tools/tile_timeline.py): wave 0 of every workgroup writes 10-ns timestamps
+                   // [tile index, start, K loop done, epilogue done] per tile it walks; NULL = no stamps
+#endif
 };
 
 // LDS swizzles (16-B chunk index XOR) for 128-B tile rows read with ds_read_b128.
@@ -440,9 +438,7 @@ __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :
 // issued between the staging units of the prologue and those of the K loop)
 template <int NS, int YMAX>
 __device__ __forceinline__ void wait_units(int y) {
-  if (YMAX >= 7 && y >= 7) wait_vm<14 + NS>();
-  else if (YMAX >= 6 && y == 6) wait_vm<12 + NS>();
-  else if (YMAX >= 5 && y == 5) wait_vm<10 + NS>();
+  if (YMAX >= 5 && y == 5) wait_vm<10 + NS>();
   else if (YMAX >= 4 && y == 4) wait_vm<8 + NS>();
   else if (y >= 3) wait_vm<6 + NS>();
   else if (y == 2) wait_vm<4 + NS>();
@@ -451,9 +447,7 @@ __device__ __forceinline__ void wait_units(int y) {
 }
 // Ring form of the pipeline above: the staging units live in R = D + 3 slots of 16 KiB (unit s in slot s mod R, its 128 rows
 // contiguous), phase ph issues unit ph + D, and D - 2 units (2 (D - 2) loads per wave) stay in flight across every barrier.  D = 5 is
-// the schedule described above in 128 KiB; D = 7 uses all 160 KiB of LDS and keeps 80 KiB per CU in flight: the K loop runs at the
-// pace (operand latency) / (look-ahead) -- the first fetch of every operand line comes from HBM or the Infinity Cache, and the
-// workgroups that share it ask for it at the same time -- so two more units in flight shorten every phase.
+// the schedule described above in 128 KiB.
 //
 // PERSIST: one workgroup per CU walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... (the same tile -> XCD assignment as one
 // workgroup per tile, gridDim.x being a multiple of 8).  The first D units of the NEXT tile are issued before the epilogue of this
@@ -462,10 +456,11 @@ __device__ __forceinline__ void wait_units(int y) {
 // CDNA counts stores in vmcnt, in issue order with the loads: an interior tile issues exactly NS output stores per lane between
 // unit D - 1 and unit D of the next tile, and the waits that retire units 1..3 allow for them; the wait that retires unit 5 (P3 of
 // K-tile 0) is the first that needs the stores acknowledged.
-template <int EPI, bool PERSIST, int D>
+constexpr int NT256_D = 5;  // look-ahead in staging units
+template <int EPI, bool PERSIST>
 __global__ __launch_bounds__(512) void gemm_nt_256_kernel(GemmNT g, int tiles) {
   constexpr int BM = 256, BN = 256, MT = 8, NT = 4;
-  constexpr int R = D + 3, UNIT = 128 * 128;
+  constexpr int D = NT256_D, R = D + 3, UNIT = 128 * 128;
   // output stores per lane of an interior tile (16-B stores; fp32 output: two per 8 columns; GELU also stores gelu')
   constexpr int NS = !PERSIST ? 0 : EPI == EPI_GELU || EPI == EPI_F32 ? 32 : EPI == EPI_F32_ACC ? 0 : 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -479,18 +474,11 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(GemmNT g, int tiles) {
   // per-lane global element offsets of the 8 (unit, instruction) loads of a tile; the K offset is added per K-tile.  Instruction i
   // of wave w fills the 1-KiB block (i*8 + w) of the unit's slot: unit rows (i*8 + w)*8 + (lane >> 3), 16-B chunk lane & 7.
   unsigned soff[4][2];
-  // K rotation: the tiles of one row panel that run at the same time on an XCD (GM row panels x 32 / GM columns) would ask for the
-  // same A lines at the same moment, and every one of them would wait out the full miss (requests merged on an in-flight fill are
-  // "hits" that cost a miss).  Column tn therefore starts its K loop at K-tile (tn mod P) * nk / P: each of the P tiles is the
-  // first to touch 1/P of the panel, and reads the rest from L2 several K-steps after a neighbour brought it in.
-  int kt0 = 0;
-  const int rot_p = g.k_rot < tiles_n ? g.k_rot : tiles_n;
   auto tile_origin = [&](int v, int& m0, int& n0) {
     int tm, tn;
     grouped_tile(xcd_remap(v, tiles), tiles_m, tiles_n, g.group_m, tm, tn);
     m0 = tm * BM;
     n0 = tn * BN;
-    kt0 = rot_p > 1 ? (tn % rot_p) * (nk / rot_p) : 0;
   };
   auto tile_offsets = [&](int m0, int n0) {
 #pragma unroll
@@ -524,9 +512,7 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(GemmNT g, int tiles) {
     iss = iss + 1 == R ? 0 : iss + 1;
     if (s >= total) return;
     const int j = s & 3;
-    int kt = (s >> 2) + kt0;
-    kt = kt >= nk ? kt - nk : kt;
-    const bf16* src = ((j == 0 || j == 3) ? g.A : g.B) + kt * 64;
+    const bf16* src = ((j == 0 || j == 3) ? g.A : g.B) + (s >> 2) * 64;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const unsigned so = j == 0 ? soff[0][i] : j == 1 ? soff[1][i] : j == 2 ? soff[2][i] : soff[3][i];
@@ -576,12 +562,6 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(GemmNT g, int tiles) {
   } while (0)
 
   int v = blockIdx.x, m0, n0;
-  if (PERSIST && g.skew_ticks > 0 && (int)blockIdx.x >= g.skew_from) {
-    // start-time skew (launch_nt_256): the workgroups that walk one tile fewer than the others start late, spread over one tile time
-    const long long t0 = wall_clock64();
-    const long long d = (long long)g.skew_ticks * ((int)blockIdx.x - g.skew_from) / ((int)gridDim.x - g.skew_from);
-    while (wall_clock64() - t0 < d) __builtin_amdgcn_s_sleep(8);
-  }
   tile_origin(v, m0, n0);
   tile_offsets(m0, n0);
   // prologue: units 0..D-1 in flight
@@ -589,12 +569,16 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(GemmNT g, int tiles) {
   for (int s = 0; s < D; ++s) issue(s);
   bool stores_behind = false;  // NS output stores of the previous tile were issued after the units 0..D-1 of this one
 
+#ifdef XFM_DIAG
   int dbg_n = 0;
+#endif
   while (true) {
+#ifdef XFM_DIAG
     if (g.dbg != nullptr && tid == 0) {
       long long* d = g.dbg + ((long)blockIdx.x * 8 + dbg_n) * 4;
       d[0] = v; d[1] = wall_clock64();
     }
+#endif
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -646,14 +630,15 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(GemmNT g, int tiles) {
       // ---- P3: (a1, b0); retire a0, b0 of the next K-tile
       issue(ph + D + 3);
       last = ph + D + 3 < total ? ph + D + 3 : total - 1;
-      if (D > 5 && plus) wait_units<NS, D - 2>(last - (ph + 5) < 0 ? 0 : last - (ph + 5));  // D > 5: units 6.. of the prologue are older than the stores too
-      else wait_units<0, D - 2>(last - (ph + 5) < 0 ? 0 : last - (ph + 5));
+      wait_units<0, D - 2>(last - (ph + 5) < 0 ? 0 : last - (ph + 5));
       XFM_BAR();
       XFM_QUAD(1, 0, wb0);
       XFM_BAR();
     }
     if (wr == 0) XFM_BAR();  // both groups are past their last LDS read
+#ifdef XFM_DIAG
     if (g.dbg != nullptr && tid == 0) g.dbg[((long)blockIdx.x * 8 + dbg_n) * 4 + 2] = wall_clock64();
+#endif
     const int cm0 = m0, cn0 = n0;
     // The bias goes out BEFORE the next tile's staging loads and is waited for with a count that leaves exactly those in flight
     // (loads return in order): this wave's 64 values, into the last ring slot (free until P2 of the next tile's first K-tile).
@@ -681,10 +666,12 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(GemmNT g, int tiles) {
     wait_units<0, D>(ahead);
     if (g.bias == nullptr) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     gemm_epilogue<MT, NT, EPI>(g, acc, cm0 + wr * 128, cn0 + wc * 64, lr, lg, lds_bias);
+#ifdef XFM_DIAG
     if (g.dbg != nullptr && tid == 0) {
       g.dbg[((long)blockIdx.x * 8 + dbg_n) * 4 + 3] = wall_clock64();
       dbg_n = dbg_n < 7 ? dbg_n + 1 : 7;
     }
+#endif
     if (!more) break;
     XFM_FENCE();
     // exactly NS stores per lane only when every lane stored every (mt, np) with one 16-B (2 x 16-B for fp32) instruction
@@ -693,15 +680,20 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(GemmNT g, int tiles) {
 #undef XFM_QUAD
 }
 
-template <int E, bool P, int D>
+#ifdef XFM_DIAG
+// Diagnostic build: where the next launches of the 256 x 256 kernel put their stamps (xfm_diag_set_timeline, capi.hip); ptr NULL = off
+static XfmTimeline nt256_timeline = {nullptr, 0, 0};
+#endif
+
+template <int E, bool P>
 static void launch_nt_256_as(const GemmNT& g, int grid, int tiles, hipStream_t st) {
-  constexpr int smem = (D + 3) * 128 * 128;
+  constexpr int smem = (NT256_D + 3) * 128 * 128;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_256_kernel<E, P, D>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_256_kernel<E, P>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     attr_set = true;
   }
-  hipLaunchKernelGGL((gemm_nt_256_kernel<E, P, D>), dim3(grid), dim3(512), smem, st, g, tiles);
+  hipLaunchKernelGGL((gemm_nt_256_kernel<E, P>), dim3(grid), dim3(512), smem, st, g, tiles);
 }
 
 static int launch_nt_256(const GemmNT& g_in, int epi, hipStream_t st) {
@@ -711,40 +703,23 @@ static int launch_nt_256(const GemmNT& g_in, int epi, hipStream_t st) {
     xfm_set_error("gemm_nt: operand too large for the 256x256 kernel's 32-bit element offsets");
     return XFM_E_ARG;
   }
-  // more tiles than CUs: one persistent workgroup per CU (XFM_GEMM_PERSIST=0: one workgroup per tile); XFM_GEMM_NT_D = look-ahead
-  // in staging units (5: 128 KiB of LDS, 7: 160 KiB)
-  static const int persist_env = getenv("XFM_GEMM_PERSIST") ? atoi(getenv("XFM_GEMM_PERSIST")) : 1;
-  static const int d_env = getenv("XFM_GEMM_NT_D") ? atoi(getenv("XFM_GEMM_NT_D")) : 5;
+  // more tiles than CUs: one persistent workgroup per CU (XFM_GEMM_PERSIST=0: one workgroup per tile)
+  static const int persist_env = xfm_env_int("XFM_GEMM_PERSIST", 1);
   static const int cus = xfm_cu_count();
   const bool persist = persist_env && cus >= 8 && tiles > cus;
   const int grid = persist ? cus & ~7 : tiles;
-  // Start-time skew.  A round of 256 tiles ends with every CU storing its 128 KB (256 KB with gelu') of output at the same moment:
-  // 33 - 66 MB that drain at the chip's write bandwidth (7 - 15 us) while no matrix core works, and the next tile's staging loads
-  // queue behind the store acknowledgements (in-order vmcnt).  tools/kstep_probe.py: 1.4 - 1.5 us per K-step but 8 - 9 us of fixed cost
-  // per round.  The workgroups that walk one tile FEWER than the others (tiles % grid != 0) can start up to one tile time later for
-  // free; spread over that time they stay out of step with the rest for the whole launch, and the stores of one group drain under the
-  // K loops of the others.  XFM_GEMM_SKEW_US: the spread in microseconds per K-step of the problem (0 = off).
-  static const float skew_env = getenv("XFM_GEMM_SKEW_US") ? (float)atof(getenv("XFM_GEMM_SKEW_US")) : 0.f;
-  g.skew_from = 0;
-  g.skew_ticks = 0;
-  g.dbg = nullptr;
-  {
-    const char* dp = getenv("XFM_GEMM_DBG_PTR");   // (read per launch: the tool sets it around the one call it wants a timeline of)
-    if (dp != nullptr && dp[0] != 0) g.dbg = reinterpret_cast<long long*>(strtoull(dp, nullptr, 0));
+#ifdef XFM_DIAG
+  g.dbg = nt256_timeline.ptr;
+  if (g.dbg != nullptr && nt256_timeline.bytes < (size_t)grid * XFM_NT256_STAMP_BYTES) {   // 8 tiles x 4 stamps per workgroup
+    xfm_set_error("gemm_nt_256: timeline buffer of %zu bytes is short of %d workgroups x %d: launched without stamps", nt256_timeline.bytes, grid,
+                  XFM_NT256_STAMP_BYTES);
+    g.dbg = nullptr;
   }
-  if (persist && skew_env > 0.f && tiles % grid != 0) {
-    g.skew_from = tiles % grid;
-    g.skew_ticks = (int)(skew_env * 100.f * (float)(g.K / 64));
-  }
-#define XFM_256_CASE(E)                                                                 \
-  case E:                                                                               \
-    if (d_env == 5) {                                                                   \
-      if (persist) launch_nt_256_as<E, true, 5>(g, grid, tiles, st);                    \
-      else launch_nt_256_as<E, false, 5>(g, grid, tiles, st);                           \
-    } else {                                                                            \
-      if (persist) launch_nt_256_as<E, true, 7>(g, grid, tiles, st);                    \
-      else launch_nt_256_as<E, false, 7>(g, grid, tiles, st);                           \
-    }                                                                                   \
+#endif
+#define XFM_256_CASE(E)                                            \
+  case E:                                                          \
+    if (persist) launch_nt_256_as<E, true>(g, grid, tiles, st);    \
+    else launch_nt_256_as<E, false>(g, grid, tiles, st);           \
     break;
   switch (epi) {
     XFM_256_CASE(EPI_BF16)
@@ -801,7 +776,7 @@ static int nt_plan(int M, int N, int K, int epi, int tile_hint, int* rows_a_out,
     // Tail split: one workgroup per CU, so T tiles of 256x256 cost ceil(T / 256) rounds.  When the last round would be
     // nearly empty (N = 768: 99 x 3 = 297 tiles = 1.16 rounds), the whole rounds run as 256x256 tiles and the remaining
     // rows go to the small-tile kernels, which fill every CU for a fraction of a big-tile time.
-    static const int split_env = getenv("XFM_GEMM_TAIL_SPLIT") ? atoi(getenv("XFM_GEMM_TAIL_SPLIT")) : 35;  // tuning knob: max tail % (35 measured best, tools/split_sweep.sh)
+    static const int split_env = xfm_env_int("XFM_GEMM_TAIL_SPLIT", 35);  // tuning knob: max tail % (35 measured best, tools/split_sweep.sh)
     const long tn256 = cdiv(N, 256), t256 = (long)cdiv(M, 256) * tn256;
     if (split_env && tile_hint == 0 && M >= 2048 && t256 > 256 && t256 % 256 != 0 && (t256 % 256) * 100 < split_env * 256) {
       const int rows_a = (int)((t256 / 256) * 256 / tn256) * 256;  // row tiles that exactly fill the whole rounds
@@ -842,6 +817,20 @@ static int nt_plan(int M, int N, int K, int epi, int tile_hint, int* rows_a_out,
   return cfg;
 }
 
+// the fields every NT launch sets; the rest (aux, K-slices) stays off
+static GemmNT gemm_nt_args(const void* A, long lda, const void* B, long ldb, void* C, long ldc, const float* bias, int M, int N, int K) {
+  static const int gm_env = xfm_env_int("XFM_GEMM_GROUP_M", 0);  // tuning knob
+  GemmNT g{};
+  g.A = (const bf16*)A; g.lda = lda;
+  g.B = (const bf16*)B; g.ldb = ldb;
+  g.C = C; g.ldc = ldc;
+  g.bias = bias;
+  g.M = M; g.N = N; g.K = K;
+  g.group_m = gm_env > 0 ? gm_env : 8;
+  g.k_splits = 1;
+  return g;
+}
+
 int xfm_gemm_nt_impl(const void* A, long lda, const void* B, long ldb, void* C, long ldc, const float* bias,
                      void* aux, long ldaux, int M, int N, int K, int epi, int tile_hint, hipStream_t st) {
   XFM_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_nt: empty problem M=%d N=%d K=%d", M, N, K);
@@ -850,9 +839,8 @@ int xfm_gemm_nt_impl(const void* A, long lda, const void* B, long ldb, void* C, 
   XFM_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 && ((uintptr_t)C % 16) == 0,
               "gemm_nt: operands must be 16-byte aligned");
   XFM_REQUIRE((epi != EPI_GELU && epi != EPI_DGELU) || aux != nullptr, "gemm_nt: epilogue %d needs aux", epi);
-  static const int gm_env = getenv("XFM_GEMM_GROUP_M") ? atoi(getenv("XFM_GEMM_GROUP_M")) : 0;  // tuning knob
-  static const int rot_env = getenv("XFM_GEMM_KROT") ? atoi(getenv("XFM_GEMM_KROT")) : 0;  // tuning knob (measured neutral)
-  GemmNT g{(const bf16*)A, lda, (const bf16*)B, ldb, C, ldc, bias, (bf16*)aux, ldaux, M, N, K, gm_env > 0 ? gm_env : 8, 1, rot_env, 0};
+  GemmNT g = gemm_nt_args(A, lda, B, ldb, C, ldc, bias, M, N, K);
+  g.aux = (bf16*)aux; g.ldaux = ldaux;
   int rows_a = 0, k_splits = 1;
   const int cfg = nt_plan(M, N, K, epi, tile_hint, &rows_a, &k_splits);
   if (rows_a > 0) {  // tail split: whole rounds of 256x256 tiles first, the remaining rows on the small-tile kernels
@@ -863,15 +851,11 @@ int xfm_gemm_nt_impl(const void* A, long lda, const void* B, long ldb, void* C, 
                             aux ? (void*)((bf16*)aux + (long)rows_a * ldaux) : nullptr, ldaux, M - rows_a, N, K, epi, -1, st);
   }
   g.k_splits = k_splits;
-  static const int exp_cfg = getenv("XFM_GEMM_EXP_CFG") ? atoi(getenv("XFM_GEMM_EXP_CFG")) : 0;  // experiment: replaces config 7 at M >= 4096
-  if (exp_cfg > 0 && tile_hint == 0 && cfg == 7 && M >= 4096 && k_splits == 1) return exp_cfg == 9 ? launch_nt<128, 128, 3>(g, epi, st) : exp_cfg == 10 ? launch_nt<128, 128, 4>(g, epi, st) : launch_nt<128, 128, 2>(g, epi, st);
   switch (cfg) {
     case 1: return launch_nt<128, 128, 2>(g, epi, st);
     case 2: return launch_nt<64, 128, 2>(g, epi, st);
     case 7: return launch_nt<64, 128, 3>(g, epi, st);
     case 8: return launch_nt<64, 64, 4>(g, epi, st);
-    case 9: return launch_nt<128, 128, 3>(g, epi, st);
-    case 10: return launch_nt<128, 128, 4>(g, epi, st);
     case 4: return launch_nt_ring(g, epi, st);
     case 5: return launch_nt_256(g, epi, st);
     default: return launch_nt<64, 64, 2>(g, epi, st);
@@ -919,8 +903,6 @@ static int ksplit_plan(int M, int N, int K, int* nk_per_out) {
     if (sp > K / 1024) sp = K / 1024;
     if (sp < 1) sp = 1;
   }
-  static const int force_env = getenv("XFM_KSPLIT_FORCE") ? atoi(getenv("XFM_KSPLIT_FORCE")) : 0;   // experiment knob
-  if (force_env > 0 && force_env <= K / 64) sp = force_env;
   const int nk_all = K / 64, nk_per = cdiv(nk_all, sp);
   *nk_per_out = nk_per;
   return cdiv(nk_all, nk_per);  // slices that own at least one K-tile
@@ -943,13 +925,13 @@ int xfm_gemm_nt_ksplit_impl(const void* A, long lda, const void* B, long ldb, vo
   XFM_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "gemm_nt_ksplit: operands must be 16-byte aligned rows");
   XFM_REQUIRE(ws != nullptr && ((uintptr_t)ws % 16) == 0 && ws_bytes >= (long)slices * M * N * 4,
               "gemm_nt_ksplit: workspace of %ld bytes needed (xfm_gemm_nt_ksplit_workspace)", (long)slices * M * N * 4);
-  static const int gm_env = getenv("XFM_GEMM_GROUP_M") ? atoi(getenv("XFM_GEMM_GROUP_M")) : 0;
-  GemmNT g{(const bf16*)A, lda, (const bf16*)B, ldb, ws, (long)N, bias, nullptr, 0, M, N, K, gm_env > 0 ? gm_env : 8, slices, 0, (long)M * N};
+  GemmNT g = gemm_nt_args(A, lda, B, ldb, ws, (long)N, bias, M, N, K);
+  g.k_splits = slices;
+  g.split_stride = (long)M * N;
   // k_splits = the slices that own K-tiles; the kernel re-derives nk_per = ceil(nk_all / k_splits) <= the planned one, under which
   // exactly those slices stay non-empty, so every plane of the workspace is written in full
   XFM_REQUIRE(cdiv(K / 64, cdiv(K / 64, slices)) == slices, "gemm_nt_ksplit: slice plan mismatch");
-  static const int tile_env = getenv("XFM_KSPLIT_TILE") ? atoi(getenv("XFM_KSPLIT_TILE")) : 0;   // experiment knob: 1 = 128 x 128 tiles
-  int rc = tile_env == 1 ? launch_nt<128, 128, 3>(g, EPI_F32, st) : launch_nt<64, 128, 3>(g, EPI_F32, st);
+  int rc = launch_nt<64, 128, 3>(g, EPI_F32, st);
   if (rc != XFM_OK) return rc;
   hipLaunchKernelGGL(ksplit_reduce_kernel, dim3(cdiv((long)M * N / 8, 256)), dim3(256), 0, st, ws, slices, (long)M * N, M, N, out, ldo, out_bf16);
   return xfm_check_launch("ksplit_reduce");
@@ -1306,19 +1288,11 @@ struct Tn256Seg {
   int n0, k0, mbeg, nk;
   bool do_bias;
   int rows;   // RAGGED: rows of this piece that exist (the last K-step of a problem whose M is no multiple of 64 is short)
-  // Progress throttle between the workgroups of ONE XCD (grouped kernel, whole tiles; window = 0: off).  The 32 workgroups of an XCD
-  // walk 32 consecutive tiles, which share their dY / X panels in groups -- 15 panels instead of 64 -- but only while they are within
-  // a few K-steps of each other: a K-step of those panels is 480 KB of the XCD's 4 MB of L2, and left alone the workgroups drift
-  // apart over the 394 K-steps of a tile (27 GB per step beyond L2 against ~7 if every shared panel were read once per XCD).  Every
-  // 4th K-step wave 0 publishes base + K-steps done in row[slot] and holds the workgroup's next barrier back while it is more than
-  // `window` K-steps ahead of the slowest of the row's n workgroups (bounded spin: a workgroup that is not resident yet, or a stale
-  // row, costs at most the bound, never a hang).
-  unsigned* row; int slot, n, window; unsigned prog0;
 };
 __device__ __attribute__((aligned(16))) const unsigned tn_zero16[4] = {0u, 0u, 0u, 0u};
 
 // RAGGED: rows at or past sg.rows are staged as zeros (their lanes point the direct-to-LDS load at a 16-byte zero constant).
-template <bool RAGGED, bool SYNC = false>
+template <bool RAGGED>
 __device__ __forceinline__ void tn256_mainloop(const Tn256Seg& sg, char* smem, f32x4 (&acc)[8][4], f32x4 (&bacc)[2]) {
   constexpr int UNIT = 64 * 256, BUF = 4 * UNIT;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -1442,20 +1416,6 @@ __device__ __forceinline__ void tn256_mainloop(const Tn256Seg& sg, char* smem, f
     const char* buf = smem + (kt & 1) * BUF;
     const int ph = 4 * kt;
     int last;
-    if (SYNC && sg.window > 0 && (kt & 3) == 0 && w == 0) {   // (see Tn256Seg; compiled into the throttled build only)
-      const unsigned mine = sg.prog0 + (unsigned)kt;
-      if (lane == 0) __hip_atomic_store(sg.row + sg.slot, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (int spin = 0; spin < 3000; ++spin) {
-        unsigned v = lane < sg.n ? __hip_atomic_load(sg.row + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xFFFFFFFFu;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-          const unsigned o = (unsigned)__shfl_xor((int)v, off, 64);
-          v = o < v ? o : v;
-        }
-        if (mine <= v + (unsigned)sg.window) break;
-        __builtin_amdgcn_s_sleep(8);
-      }
-    }
     // ---- P0: (a0, b0)
     issue(ph + 5);
     read_a(buf + 0 * UNIT);
@@ -1591,9 +1551,6 @@ struct TnGroup {
   long sk_iters;             // (total_tiles - full_tiles) * nk
   float* ws;
   float* ws_bias;            // 256 floats per partial-piece slot, behind the slots' tiles
-  unsigned* prog;            // progress rows of the XCDs (8 x 64 words; Tn256Seg::row), epoch << 20 | K-steps done
-  unsigned epoch;
-  int window;                // 0: no throttle
   TnGroupProb p[TN_GROUP_MAX];
 };
 __host__ __device__ __forceinline__ long tn_sk_bound(long R, int nk, int sk_wgs, int i) {
@@ -1604,8 +1561,6 @@ __host__ __device__ __forceinline__ long tn_sk_bound(long R, int nk, int sk_wgs,
   return raw;
 }
 
-// SYNC: the build with the XCD progress throttle (XFM_TN_SYNC_WINDOW; the default build carries none of its registers)
-template <bool SYNC>
 __global__ __launch_bounds__(512) void gemm_tn_group_kernel(TnGroup G) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int wg = xcd_remap(blockIdx.x, gridDim.x), nwg = gridDim.x;
@@ -1617,15 +1572,6 @@ __global__ __launch_bounds__(512) void gemm_tn_group_kernel(TnGroup G) {
   }
   const long sk_a = sk_pos;
   bool first = true;
-  int tiles_done = 0;
-  bool left = false;
-  auto leave_rounds = [&]() {
-    if (SYNC && G.window > 0 && !left && threadIdx.x == 0) {
-      const int per_xcd = nwg >> 3;
-      __hip_atomic_store(G.prog + (wg / per_xcd) * 64 + wg % per_xcd, (G.epoch << 20) + 0xFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    left = true;
-  };
   for (;;) {   // (everything that steers this loop is a function of blockIdx: uniform over the workgroup)
     int tile, it0, it1;
     long slot = -1;   // >= 0: partial piece
@@ -1645,7 +1591,6 @@ __global__ __launch_bounds__(512) void gemm_tn_group_kernel(TnGroup G) {
     } else {
       break;
     }
-    if (tile >= G.full_tiles) leave_rounds();   // (past its whole tiles: nobody waits for this workgroup any more)
     if (!first) __syncthreads();   // the previous piece's LDS reads are over before this one's staging lands
     first = false;
     int pi = 0;
@@ -1653,18 +1598,9 @@ __global__ __launch_bounds__(512) void gemm_tn_group_kernel(TnGroup G) {
     const TnGroupProb& P = G.p[pi];
     const int tl = tile - (pi > 0 ? G.p[pi - 1].tile_end : 0);
     const int n0 = (tl / P.tiles_k) * 256, k0 = (tl % P.tiles_k) * 256;
-    Tn256Seg sg{P.dY, P.X, P.ldy, P.ldx, n0, k0, it0 * 64, it1 - it0, P.dbias != nullptr && k0 == 0, G.M - it0 * 64, nullptr, 0, 0, 0, 0u};
-    if (SYNC && G.window > 0 && slot < 0 && it0 == 0 && it1 == G.nk && tile < G.full_tiles) {   // a whole tile of the data-parallel rounds
-      const int per_xcd = nwg >> 3;
-      sg.row = G.prog + (wg / per_xcd) * 64;
-      sg.slot = wg % per_xcd;
-      sg.n = per_xcd < 64 ? per_xcd : 64;
-      sg.window = G.window;
-      sg.prog0 = (G.epoch << 20) + (unsigned)(tiles_done * G.nk);
-    }
+    const Tn256Seg sg{P.dY, P.X, P.ldy, P.ldx, n0, k0, it0 * 64, it1 - it0, P.dbias != nullptr && k0 == 0, G.M - it0 * 64};
     f32x4 acc[8][4], bacc[2];
-    tn256_mainloop<true, SYNC>(sg, smem, acc, bacc);
-    if (SYNC && sg.window > 0) ++tiles_done;
+    tn256_mainloop<true>(sg, smem, acc, bacc);
     if (slot >= 0) {
       if (sg.do_bias) tn256_bias_part(G.ws_bias + slot * 256, bacc);
       tn256_store_partial(G.ws, slot, acc);
@@ -1673,7 +1609,6 @@ __global__ __launch_bounds__(512) void gemm_tn_group_kernel(TnGroup G) {
       tn256_add_out<false>(P.dW, P.ldw, n0, k0, acc);
     }
   }
-  leave_rounds();
 }
 
 // the cut tiles: dW += the pieces in workgroup order.  grid (64, cut tiles): one thread per accumulator quad, as tn_reduce_kernel.
@@ -1783,7 +1718,7 @@ static int tn256_body_rows(int M, int N, int K) {
   const int M0 = M - M % 64;
   // (from 8192 rows: at the fusion tower's packed M ~ 5200 the 7 x 36 workgroups of the 256 x 256 plan walk 12 K-steps each and lose to
   // the ring kernel -- 73 vs 56 us at 5252 x 3072 x 768; round 3 had put those calls here too)
-  static const int min_rows = getenv("XFM_TN256_RAGGED_MIN") ? atoi(getenv("XFM_TN256_RAGGED_MIN")) : 8192;  // A/B knob
+  static const int min_rows = xfm_env_int("XFM_TN256_RAGGED_MIN", 8192);  // A/B knob
   if (M % 64 == 0 || M0 < min_rows || N % 256 != 0 || K % 256 != 0) return 0;
   int splits, mps;
   return tn256_plan(M0, N, K, splits, mps) >= 18 ? M0 : 0;
@@ -1858,7 +1793,7 @@ int xfm_gemm_tn_impl(const void* dY, long ldy, const void* X, long ldx, float* d
                               (int)smem);
     attr_set = true;
   }
-  static const int ring_env = getenv("XFM_TN_RING") ? atoi(getenv("XFM_TN_RING")) : 1;  // A/B knob
+  static const int ring_env = xfm_env_int("XFM_TN_RING", 1);  // A/B knob
   const bool ring = ring_env && N % 128 == 0 && K % 128 == 0 && splits_hint != -5;
   TnBatch one{};
   one.nb = 1;
@@ -1962,7 +1897,6 @@ static void tn_group_plan(int tiles, int nk, int G, int& full, int& sk_wgs, long
     if (sk_wgs < 1) sk_wgs = 1;
   }
 }
-#define TN_PROG_BYTES 2048   // 8 XCDs x 64 progress words (TnGroup::prog), at the END of the caller's workspace
 long xfm_gemm_tn_group_workspace_impl(int n, const xfm_tn_item* items, int M) {
   if (n <= 0 || items == nullptr || M <= 0) return 0;
   const int G = tn_group_cus();
@@ -1973,7 +1907,7 @@ long xfm_gemm_tn_group_workspace_impl(int n, const xfm_tn_item* items, int M) {
     int full, sk;
     long R;
     tn_group_plan(tiles, cdiv(M, 64), G, full, sk, R);
-    const long b = (sk > 1 ? 2l * sk * (256 * 256 + 256) * 4 : 0) + TN_PROG_BYTES;   // two partial-piece slots per sharing workgroup (tile + column sums) + the progress rows
+    const long b = sk > 1 ? 2l * sk * (256 * 256 + 256) * 4 : 0;   // two partial-piece slots per sharing workgroup (tile + column sums)
     need = b > need ? b : need;
     tiles = np = 0;
   };
@@ -1998,8 +1932,7 @@ int xfm_gemm_tn_group_impl(int n, const xfm_tn_item* items, int M, float* worksp
   static bool attr_set = false;
   const size_t smem = 2 * 4 * 64 * 256;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_group_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_group_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr_set = true;
   }
   TnGroup g{};
@@ -2011,18 +1944,7 @@ int xfm_gemm_tn_group_impl(int n, const xfm_tn_item* items, int M, float* worksp
     tn_group_plan(g.total_tiles, g.nk, G, g.full_tiles, g.sk_wgs, g.sk_iters);
     g.ws_bias = g.ws != nullptr ? g.ws + 2l * g.sk_wgs * 256 * 256 : nullptr;
     const int grid = g.full_tiles > 0 ? G : g.sk_wgs;
-    // progress throttle of the data-parallel rounds (XFM_TN_SYNC_WINDOW K-steps; 0 = off): needs whole rounds, 8 equal XCD shares and
-    // the progress rows at the end of the workspace
-    static const int window_env = getenv("XFM_TN_SYNC_WINDOW") ? atoi(getenv("XFM_TN_SYNC_WINDOW")) : 0;
-    static unsigned epoch = 0;
-    g.window = 0;
-    if (window_env > 0 && g.full_tiles >= grid && grid % 8 == 0 && grid / 8 <= 64 && workspace != nullptr && workspace_bytes >= TN_PROG_BYTES) {
-      g.window = window_env;
-      g.prog = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + (workspace_bytes - TN_PROG_BYTES) / 16 * 16);
-      g.epoch = (++epoch) & 0xFFFu;
-    }
-    if (g.window > 0) hipLaunchKernelGGL(gemm_tn_group_kernel<true>, dim3(grid), dim3(512), smem, st, g);
-    else hipLaunchKernelGGL(gemm_tn_group_kernel<false>, dim3(grid), dim3(512), smem, st, g);
+    hipLaunchKernelGGL(gemm_tn_group_kernel, dim3(grid), dim3(512), smem, st, g);
     int rc = xfm_check_launch("gemm_tn_group");
     if (rc == XFM_OK && g.sk_wgs > 1) {
       hipLaunchKernelGGL(tn_group_fixup_kernel, dim3(64, g.total_tiles - g.full_tiles), dim3(256), 0, st, g);

@@ -8,7 +8,6 @@
 //   mode LS    : x' = x + s_b * gamma_ls * h ; y = LN(x')    beit2.py:203-204 (layer-scale + drop-path residual)
 //                                                            fused with the LayerNorm that consumes x' next
 #include "common.h"
-#include <stdlib.h>
 
 enum { LN_PLAIN = 0, LN_POST = 1, LN_LS = 2 };
 
@@ -521,9 +520,9 @@ int xfm_reduce_sets_batch_impl(int n, const xfm_reduce_item* items, hipStream_t 
 }
 
 int xfm_ln_bwd_grid(int rows) {
-  static const int rpb = getenv("XFM_LN_BWD_ROWS") ? atoi(getenv("XFM_LN_BWD_ROWS")) : 8;  // tuning knob (8 measured: fusion tower 13.95 -> 13.56 ms)
+  static const int rpb = xfm_env_int("XFM_LN_BWD_ROWS", 8);  // tuning knob (8 measured: fusion tower 13.95 -> 13.56 ms)
   int blocks = cdiv(rows, rpb);  // rows per workgroup: enough waves per CU for an HBM-bound kernel at M = 7680
-  static const int cap = getenv("XFM_LN_BWD_BLOCKS") ? atoi(getenv("XFM_LN_BWD_BLOCKS")) : 768;  // tuning knob
+  static const int cap = xfm_env_int("XFM_LN_BWD_BLOCKS", 768);  // tuning knob
   if (blocks > cap) blocks = cap;  // 3 blocks (12 waves) per CU: the kernel is HBM-bound and needs the loads in flight
   if (blocks < 1) blocks = 1;
   return blocks;
