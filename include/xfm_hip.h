@@ -231,11 +231,14 @@ typedef struct {
 
 int xfm_attn_fwd(const xfm_attn_args* a, void* stream);
 int xfm_attn_bwd(const xfm_attn_args* a, void* stream);
-/* bytes of `dbias_ws` an xfm_attn_bwd call with these arguments wants (0: none).  Long dense unmasked problems with a bias gradient
- * (Sk > 256: the 577 / 901 tokens of the 384 / 480 px ViT) sum dS over the batch inside a kernel that walks the batch entries of a
- * slice with a 128 x 128 block of the gradient in registers; with more than one slice the per-slice sums are [slices, H, Sq, bias_ld]
- * planes in this workspace (a few MB) that a second kernel folds into dbias in slice order.  The general kernels (masked / dropped
- * problems) still take the [B, H, Sq, bias_ld] form described at xfm_attn_args.dbias_ws. */
+/* bytes of `dbias_ws` an xfm_attn_bwd call with these arguments wants (0: none): the planes of [H, Sq, bias_ld] floats of the route
+ * that the call's backward plan picks (csrc/attention.hip, attn_bwd_plan -- the dispatcher runs the same plan, and uses a workspace
+ * only where this function asks for one).  Long dense unmasked problems with a bias gradient (Sk > 256: the 577 / 901 tokens of the
+ * 384 / 480 px ViT) sum dS over the batch inside a kernel that walks the batch entries of a slice with a 128 x 128 block of the
+ * gradient in registers: one plane per slice when there is more than one (a few MB), folded into dbias in slice order by a second
+ * kernel.  The general kernels (masked / dropped problems, Sk > 256) take the B planes described at xfm_attn_args.dbias_ws.  Short
+ * problems (Sk <= 256) want none, or with XFM_DETERMINISTIC=1 one plane per batch slice of the short dQ kernel.  A workspace that
+ * is NULL, or whose bias rows (bias_ld) reach past the last 64-key chunk, is not used: atomics, or one slice. */
 long xfm_attn_bwd_workspace(const xfm_attn_args* a);
 /* dense additive bias [H,S,ld] (fp32) -> two tiled copies, each [H][T][T][64 lanes][4] floats with T = ceil(S / 16), pre-divided by
  * `scale` (the kernels start the score accumulators from bias / scale):

@@ -195,3 +195,101 @@ def test_environment_knobs_have_one_reader_and_a_documented_name():
     table = open(os.path.join(ROOT, "tools", "README.md")).read()
     documented = set(re.findall(r"XFM_[A-Z0-9_]+", table))
     assert read <= documented, sorted(read - documented)
+
+
+ATTENTION_SOURCES = ("attention.hip", "attention_common.h", "attention_general.hip", "attention_short.hip", "attention_grouped.hip",
+                     "attention_vit.hip", "attention_long.hip", "attention_aux.hip")
+
+
+def _attn_ws_args(B, H, Sq, Sk, ld=None, dbias=True, mask=False, phase=0, single_pass=False):
+    """xfm_attn_args of a dense backward call with an additive bias (rows padded to a multiple of 16 keys unless `ld` says otherwise)
+    and dummy non-NULL, 16-byte aligned pointers: xfm_attn_bwd_workspace is host-only and dereferences none of them."""
+    from xfm_amd import _lib
+    a = _lib.AttnArgs()
+    P = 0x10000
+    for f in ("q", "k", "v", "o", "lse", "bias", "dout", "dq", "dk", "dv", "delta", "bias_t", "o_lo", "bias_tiled", "bias_t_tiled"):
+        setattr(a, f, P)
+    for f in ("q_rs", "k_rs", "v_rs", "o_rs", "do_rs", "dq_rs", "dk_rs", "dv_rs"):
+        setattr(a, f, 64 * H)
+    a.B, a.H, a.Sq, a.Sk, a.scale, a.bwd_phase = B, H, Sq, Sk, 0.125, phase
+    a.bias_ld = ld if ld is not None else (Sk + 15) // 16 * 16
+    a.bias_t_ld = a.stat_ld = (Sq + 15) // 16 * 16
+    a.dbias = P if dbias else None
+    a.key_keep = P if mask else None
+    if single_pass:   # what the opt-in single-pass ViT backward wants: the forward's O without its low half
+        a.o_lo = None
+    return a
+
+
+# (arguments of _attn_ws_args, environment, bytes).  The values are those of the library BEFORE the backward plan existed (two
+# derivations of the route, one in the dispatcher and one here), recorded from it; the two rows marked "discarded" are the exception:
+# there it asked for a buffer that its own dispatcher then dropped, and the plan asks for none.
+ATTN_WORKSPACE_TABLE = [
+    (dict(B=9, H=12, Sq=197, Sk=197), {}, 0),                                                 # short pair, atomics
+    (dict(B=9, H=12, Sq=197, Sk=197), {"XFM_DETERMINISTIC": "1"}, 5900544),                   # ... 3 slices x [12, 197, 208] planes
+    (dict(B=64, H=12, Sq=197, Sk=197), {"XFM_DETERMINISTIC": "1"}, 7867392),                  # 4 slices
+    (dict(B=128, H=12, Sq=197, Sk=197), {"XFM_DETERMINISTIC": "1"}, 7867392),
+    (dict(B=9, H=12, Sq=197, Sk=197, phase=2), {"XFM_DETERMINISTIC": "1"}, 0),                # dK/dV alone: no bias gradient
+    (dict(B=9, H=12, Sq=197, Sk=197, phase=1), {"XFM_DETERMINISTIC": "1"}, 5900544),
+    (dict(B=9, H=12, Sq=197, Sk=197, dbias=False), {"XFM_DETERMINISTIC": "1"}, 0),
+    (dict(B=9, H=12, Sq=197, Sk=197, ld=224), {"XFM_DETERMINISTIC": "1"}, 0),                 # rows wider than the key tiles: atomics
+    (dict(B=9, H=2, Sq=40, Sk=40), {"XFM_DETERMINISTIC": "1"}, 138240),                       # 9 slices x [2, 40, 48]
+    (dict(B=9, H=2, Sq=40, Sk=40), {"XFM_DETERMINISTIC": "0"}, 0),
+    (dict(B=3, H=12, Sq=30, Sk=30), {"XFM_DETERMINISTIC": "1"}, 138240),
+    (dict(B=3, H=12, Sq=30, Sk=30), {}, 0),
+    (dict(B=1, H=12, Sq=197, Sk=197), {"XFM_DETERMINISTIC": "1"}, 0),                         # one slice
+    (dict(B=3, H=12, Sq=30, Sk=30, mask=True), {"XFM_DETERMINISTIC": "1"}, 0),                # masked, resident: atomics
+    (dict(B=5, H=2, Sq=577, Sk=577), {}, 8198016),                                            # long: 3 slices x [2, 577, 592]
+    (dict(B=5, H=2, Sq=577, Sk=577), {"XFM_DETERMINISTIC": "1"}, 8198016),
+    (dict(B=5, H=2, Sq=577, Sk=577, dbias=False), {}, 0),
+    (dict(B=5, H=2, Sq=577, Sk=577), {"XFM_ATTN_LONG": "0"}, 13663360),                       # general kernel: [5, 2, 577, 592] per entry
+    (dict(B=5, H=2, Sq=577, Sk=577, mask=True), {}, 13663360),
+    (dict(B=9, H=1, Sq=260, Sk=258), {}, 2545920),
+    (dict(B=9, H=1, Sq=260, Sk=258), {"XFM_DETERMINISTIC": "1"}, 2545920),
+    (dict(B=1, H=2, Sq=130, Sk=300), {}, 0),                                                  # long, one slice: adds in place
+    (dict(B=1, H=2, Sq=130, Sk=300), {"XFM_DETERMINISTIC": "1"}, 0),
+    (dict(B=1, H=2, Sq=130, Sk=300, mask=True), {}, 316160),
+    (dict(B=1, H=2, Sq=130, Sk=300, mask=True), {"XFM_DETERMINISTIC": "1"}, 316160),
+    (dict(B=1, H=2, Sq=130, Sk=300, mask=True, ld=384), {}, 0),                               # discarded (399360): rows past the key chunks
+    (dict(B=3, H=2, Sq=197, Sk=197, single_pass=True), {"XFM_ATTN_VIT_BWD": "4"}, 983424),    # block kernel: 3 slices x [2, 197, 208]
+    (dict(B=64, H=12, Sq=197, Sk=197, single_pass=True), {"XFM_ATTN_VIT_BWD": "4"}, 9834240),   # 5 slices
+    (dict(B=9, H=12, Sq=197, Sk=197, single_pass=True), {"XFM_ATTN_VIT_BWD": "3", "XFM_DETERMINISTIC": "1"}, 0),   # discarded (5900544)
+]
+
+
+def test_attention_backward_workspace_table():
+    """xfm_attn_bwd_workspace over a fixed table of argument sets.  One process per row: XFM_ATTN_LONG is read once per process, and a
+    fresh process shows that the answer does not depend on an earlier call.  (The child loads the library alone: no GPU, no torch.)"""
+    import subprocess
+    import sys
+    from xfm_amd import build
+    child = ("import ctypes, sys\n"
+             "f = ctypes.CDLL(sys.argv[1]).xfm_attn_bwd_workspace\n"
+             "f.restype = ctypes.c_long\n"
+             "for line in sys.stdin:\n"
+             "    print(f(ctypes.c_char_p(bytes.fromhex(line.strip()))))\n")
+    by_env = {}
+    for i, (kw, env, _) in enumerate(ATTN_WORKSPACE_TABLE):
+        by_env.setdefault(tuple(sorted(env.items())), []).append(i)
+    got = {}
+    for env, rows in by_env.items():
+        e = {k: v for k, v in os.environ.items() if not k.startswith("XFM_")}
+        e.update(dict(env))
+        r = subprocess.run([sys.executable, "-c", child, build.build()], input="".join(bytes(_attn_ws_args(**ATTN_WORKSPACE_TABLE[i][0])).hex() + "\n" for i in rows),
+                           env=e, capture_output=True, text=True, check=True)
+        got.update(zip(rows, map(int, r.stdout.split())))
+    assert [got[i] for i in range(len(ATTN_WORKSPACE_TABLE))] == [w for _, _, w in ATTN_WORKSPACE_TABLE], \
+        [(kw, env, got[i], w) for i, (kw, env, w) in enumerate(ATTN_WORKSPACE_TABLE) if got[i] != w]
+
+
+def test_attention_sources_set_the_lds_attribute_once_and_include_at_the_top():
+    """One launcher owns hipFuncAttributeMaxDynamicSharedMemorySize for every attention kernel instantiation, and attention.hip (the host
+    side) pulls in its kernel families before its first function: no file order to work around."""
+    csrc = os.path.join(ROOT, "xfm_amd", "csrc")
+    assert sorted(f for f in os.listdir(csrc) if f.startswith("attention")) == sorted(ATTENTION_SOURCES)
+    text = {f: open(os.path.join(csrc, f)).read() for f in ATTENTION_SOURCES}
+    assert sum(s.count("hipFuncSetAttribute") for s in text.values()) == 1
+    lines = text["attention.hip"].splitlines()
+    first_fn = next(i for i, l in enumerate(lines) if re.match(r"^(static |int |long |template |__global__ |struct |enum )", l))
+    includes = [i for i, l in enumerate(lines) if l.lstrip().startswith("#include")]
+    assert includes and max(includes) < first_fn, (includes, first_fn)

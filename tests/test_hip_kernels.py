@@ -533,6 +533,40 @@ def test_attention_fwd_bwd(B, H, Sq, Sk, use_bias, use_keep, causal):
         _close(dkv2[:, D:], vr.grad, 2e-2, "dv (bias_t)")
 
 
+def test_short_attention_backward_bias_gradient_planes(monkeypatch):
+    """The short dQ kernel's ordered bias gradient (XFM_DETERMINISTIC=1): B = 9, H = 2, 40 x 40 is one query group and nine batch slices
+    of one entry, so each slice stores its sums into its own [H, Sq, 48] plane of the workspace that xfm_attn_bwd_workspace sized
+    (138240 bytes) and dbias_reduce_kernel folds the planes in slice order: same values as the fp32 reference within the bound of
+    test_attention_fwd_bwd, and the same bits from two runs.  XFM_DETERMINISTIC=0 (float atomics): the same bound."""
+    Fx = _fx()
+    B, H, S, ld, scale = 9, 2, 40, 48, 0.125
+    D = H * 64
+    q, kv, dout = _rand((B * S, D), seed=50), _rand((B * S, 2 * D), seed=51), _rand((B * S, D), seed=53)
+    k, v = kv[:, :D], kv[:, D:]
+    bias = _rand((H, S, ld), 1.0, F32, seed=52)
+    qr, kr, vr = (t.float().clone().requires_grad_(True) for t in (q, k, v))
+    br = bias.clone().requires_grad_(True)
+    _attn_ref(qr, kr, vr, B, H, S, S, scale, br).backward(dout.float())
+    o, lse = Fx.attn_fwd(q, k, v, B, H, S, S, scale, bias=bias)
+
+    def run():
+        dq = torch.empty((B * S, D), dtype=BF16, device="cuda")
+        dkv = torch.empty((B * S, 2 * D), dtype=BF16, device="cuda")
+        dbias = torch.zeros_like(bias)
+        Fx.attn_bwd(dout, q, k, v, o, lse, dq, dkv[:, :D], dkv[:, D:], B, H, S, S, scale, bias=bias, dbias=dbias)
+        _close(dq, qr.grad, 2e-2, "dq")
+        _close(dkv[:, :D], kr.grad, 2e-2, "dk")
+        _close(dkv[:, D:], vr.grad, 2e-2, "dv")
+        _close(dbias[:, :, :S], br.grad[:, :, :S], 2e-2, "dbias")
+        return dbias
+
+    monkeypatch.setenv("XFM_DETERMINISTIC", "1")
+    first = run()
+    assert torch.equal(first, run())
+    monkeypatch.setenv("XFM_DETERMINISTIC", "0")
+    run()
+
+
 @pytest.mark.parametrize("B,H,Sq,Sk,use_bias,use_keep,drop_p", [(3, 12, 197, 197, True, False, 0.0), (2, 4, 577, 577, True, False, 0.0),
                                                                   (5, 12, 30, 30, False, True, 0.0), (5, 12, 30, 30, False, True, 0.1),
                                                                   (4, 12, 30, 197, False, False, 0.1)])
@@ -1274,7 +1308,7 @@ def test_small_ce_any_class_count_and_ignored_labels(C):
     (3, 2, 40, False),      # waves without a key tile; no bias
 ])
 def test_short_attention_backward_delta_from_output(B, H, S, use_bias, monkeypatch):
-    """The short-sequence dQ kernel's opt-in form (XFM_ATTN_SHORT_PRE=1, csrc/attention.hip attn_bwd_dq_short_kernel<.., PRE = true>):
+    """The short-sequence dQ kernel's opt-in form (XFM_ATTN_SHORT_PRE=1, csrc/attention_short.hip attn_bwd_dq_short_kernel<.., PRE = true>):
     the softmax-gradient row term delta_i = dO_i . (O_i + Olo_i) from the forward's output halves instead of the exchange of
     sum_j P_ij dP_ij between the key-range waves.  Held to the same tolerances against fp32 math as the default form, and to the
     default form's own results within bf16 noise; the returned delta to dO . O."""

@@ -3,7 +3,7 @@ exchange path (no o_lo) and an fp32 torch reference of the same problem.  Run on
 import os
 import sys
 
-os.environ.setdefault("XFM_ATTN_SHORT_PRE", "1")   # (opt-in path: see csrc/attention.hip launch_attn_bwd)
+os.environ.setdefault("XFM_ATTN_SHORT_PRE", "1")   # (opt-in path: see csrc/attention_short.hip launch_attn_bwd_dq_short)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402

@@ -1,4 +1,4 @@
-"""Where does an entry's time go in the short attention backward's dQ kernel (ViT: 197 x 197, csrc/attention.hip
+"""Where does an entry's time go in the short attention backward's dQ kernel (ViT: 197 x 197, csrc/attention_short.hip
 attn_bwd_dq_short_kernel)?  Wave 0 of every workgroup stamps nine points of every batch entry it walks (10-ns clock, kernel argument
 `dbg`, diagnostic library only):
   top | fetched registers + the entry's K / V DMA have landed (vmcnt 0) | barrier 1 passed | next entry's K / V LDS-DMA issued |

@@ -24,26 +24,8 @@
 #define LB_SLOT_DKV (ATTN_SLOT + LB_STAT)             // Q | dO tile of 64 queries | lse | delta
 #define LB_LOG2E 1.44269504088896341f
 
-__device__ __forceinline__ void lb_wait_vm(int n) {  // wave-uniform n
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
 // A 16-byte register load the COMPILER DOES NOT TRACK (it would place `s_waitcnt vmcnt(0)` in front of the first use and drain the
-// direct-to-LDS prefetch that was issued after it).  The caller waits with lb_wait_vm(...) and then passes the value through
+// direct-to-LDS prefetch that was issued after it).  The caller waits with wait_vm(...) and then passes the value through
 // lb_use() so that no use can be scheduled ahead of the wait.
 __device__ __forceinline__ f32x4 lb_load_f32x4(const float* p) {
   f32x4 v;
@@ -59,12 +41,7 @@ __device__ __forceinline__ void lb_piece(char* tile, const bf16* g, long rs, int
   gr = gr < nvalid ? gr : nvalid - 1;
   const bf16* src = g + (long)gr * rs + c * 8;
   const unsigned dst = (unsigned)(uintptr_t)LDS_PTR(void, tile) + (unsigned)__builtin_amdgcn_readfirstlane(piece * 1024);
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory", "m0");
-}
-__device__ __forceinline__ void lb_barrier() {  // raw barrier: LDS-DMA stays in flight across it
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  lds_dma16(src, dst);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -149,12 +126,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_long_kernel(AttnArgs a, int q
 
   for (int pass = fast ? 1 : 0; pass < 2; ++pass) {
     // pass 0 (no O_lo): delta_i = sum_j P_ij dP_ij, from the same P and dP that form dS in pass 1; pass 1: dS, dQ
-    if (pass == 1 && !fast) lb_barrier();  // every wave is done with the ring slots of pass 0
+    if (pass == 1 && !fast) raw_barrier();  // every wave is done with the ring slots of pass 0
     stage(0);
     if (nchunks > 1) stage(1);
     for (int kc = 0; kc < nchunks; ++kc) {
-      lb_wait_vm(kc + 1 < nchunks ? NP : 0);  // this wave's pieces of chunk kc have landed (chunk kc + 1 may still fly)
-      lb_barrier();                           // ... everyone's; and everyone is done reading the slot chunk kc + 2 goes to
+      wait_vm(kc + 1 < nchunks ? NP : 0);  // this wave's pieces of chunk kc have landed (chunk kc + 1 may still fly)
+      raw_barrier();                           // ... everyone's; and everyone is done reading the slot chunk kc + 2 goes to
       const bool more = kc + 2 < nchunks;
       // the bias segments go out before the score MFMAs and are waited for after them (prefetching them a whole chunk ahead, in a
       // second register set, measured 13 % SLOWER: 64 more live registers, K / V fragments read twice)
@@ -193,7 +170,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_long_kernel(AttnArgs a, int q
         }
       }
       if (BIAS) {
-        lb_wait_vm(more ? NP : 0);  // the bias segments are in (they are older than chunk kc + 2's pieces)
+        wait_vm(more ? NP : 0);  // the bias segments are in (they are older than chunk kc + 2's pieces)
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
@@ -340,8 +317,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_long_kernel(AttnArgs a, int 
   stage(0);
   if (nchunks > 1) stage(1);
   for (int qc = 0; qc < nchunks; ++qc) {
-    lb_wait_vm(qc + 1 < nchunks ? n_dma : 0);
-    lb_barrier();
+    wait_vm(qc + 1 < nchunks ? n_dma : 0);
+    raw_barrier();
     const bool more = qc + 2 < nchunks;
     // transposed-bias segments of both 32-query halves of the chunk go out first (8 loads), then the next chunk's pieces
     f32x4 bt[2][2][2];  // [half][key tile][query tile of the half]
@@ -387,7 +364,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_long_kernel(AttnArgs a, int 
       }
       if (BIAS) {
         // half 0: the 4 loads of half 1 and chunk qc + 2's pieces are younger; half 1: only the pieces
-        lb_wait_vm((s2 == 0 ? 4 : 0) + (more ? n_dma : 0));
+        wait_vm((s2 == 0 ? 4 : 0) + (more ? n_dma : 0));
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -516,8 +493,8 @@ __global__ __launch_bounds__(512) void attn_dbias_long_kernel(AttnArgs a, int qb
   if (b_begin < b_end) stage(b_begin, 0);
   for (int b = b_begin; b < b_end; ++b) {
     const int buf = (b - b_begin) & 1;
-    lb_wait_vm(0);   // entry b has landed (nothing younger is in flight here)
-    lb_barrier();    // ... everyone's pieces; everyone is done with entry b - 1 (the other buffer)
+    wait_vm(0);   // entry b has landed (nothing younger is in flight here)
+    raw_barrier();    // ... everyone's pieces; everyone is done with entry b - 1 (the other buffer)
     if (b + 1 < b_end) stage(b + 1, buf ^ 1);
     (void)n_dma;
     const char* base = lds + buf * LD_STAGE;
@@ -594,90 +571,43 @@ static bool attn_long_shape(const AttnArgs& a) {
          // the bias-gradient kernel writes every column of a plane row: the row must end inside the last 128-key block
          (a.dbias == nullptr || (a.bias != nullptr && a.bias_ld <= (long)cdiv(a.Sk, 128) * 128 && ((uintptr_t)a.dbias % 16) == 0));
 }
-// XFM_ATTN_VIT_BWD=4 (experiment): the single-pass backward WITHOUT its bias-gradient sums (they are what spills it) + this file's
-// block-walking bias-gradient kernel on the delta it wrote
-static bool attn_vit_split_dbias(const AttnArgs& a) {
-  return xfm_env_int("XFM_ATTN_VIT_BWD", 0) == 4 && a.dbias != nullptr && attn_vit3_shape(a) && a.bias_ld % 4 == 0 && a.bias_ld <= (long)cdiv(a.Sk, 128) * 128 &&
-         ((uintptr_t)a.dbias % 16) == 0 && ((uintptr_t)a.bias % 16) == 0;
+// the bias-gradient kernel alone takes this problem (the conditions attn_long_shape puts on bias / dbias)
+static bool attn_dbias_blocks_ok(const AttnArgs& a) {
+  return a.bias_ld % 4 == 0 && a.bias_ld <= (long)cdiv(a.Sk, 128) * 128 && ((uintptr_t)a.dbias % 16) == 0 && ((uintptr_t)a.bias % 16) == 0;
 }
-long xfm_attn_bwd_workspace_impl(const AttnArgs& a) {
-  if (attn_vit_split_dbias(a)) {
-    const int blocks = cdiv(a.Sq, 128) * cdiv(a.Sk, 128) * a.H;
-    const int slices = dbias_long_slices(blocks, a.B, (long)a.H * a.Sq * a.bias_ld * 4);
-    return slices > 1 ? (long)slices * a.H * a.Sq * a.bias_ld * 4 : 0;
-  }
-  if (attn_short_dbias_planes(a)) {   // XFM_DETERMINISTIC: one plane per batch slice of the short dQ kernel
-    int groups, nb;
-    return (long)attn_short_dq_slices(a, groups, nb) * a.H * a.Sq * a.bias_ld * 4;
-  }
-  if (a.dbias == nullptr || a.Sk <= 64 * ATTN_RES_MAX) return 0;
-  if (attn_long_shape(a)) {
-    const int blocks = cdiv(a.Sq, 128) * cdiv(a.Sk, 128) * a.H;
-    const int slices = dbias_long_slices(blocks, a.B, (long)a.H * a.Sq * a.bias_ld * 4);
-    return slices > 1 ? (long)slices * a.H * a.Sq * a.bias_ld * 4 : 0;
-  }
-  return (long)a.B * a.H * a.Sq * a.bias_ld * 4;  // the general dQ kernel's per-entry dS (xfm_attn_args.dbias_ws)
+static int attn_dbias_blocks_slices(const AttnArgs& a) {
+  return dbias_long_slices(cdiv(a.Sq, 128) * cdiv(a.Sk, 128) * a.H, a.B, (long)a.H * a.Sq * a.bias_ld * 4);
 }
-
-template <typename K>
-static void long_attr(K kernel, int bytes) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
 // the accumulator-layout bias copies (xfm_bias_tile) serve square problems
 static bool long_tiled(const AttnArgs& a, const float* tiles) { return a.bias != nullptr && tiles != nullptr && a.Sq == a.Sk && ((uintptr_t)tiles % 16) == 0; }
+// the dK/dV kernel reads the transposed bias copy; without one that half stays on the general kernel
+static bool attn_long_dkv_ok(const AttnArgs& a) { return a.bias == nullptr || a.bias_t != nullptr || long_tiled(a, a.bias_t_tiled); }
 
-static int launch_attn_dbias_blocks(const AttnArgs& a, hipStream_t st);
 static int launch_attn_bwd_long_dq(const AttnArgs& a, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    long_attr(attn_bwd_dq_long_kernel<true, true>, LB_RING * LB_SLOT_DQ);
-    long_attr(attn_bwd_dq_long_kernel<true, false>, LB_RING * LB_SLOT_DQ);
-    long_attr(attn_bwd_dq_long_kernel<false, false>, LB_RING * LB_SLOT_DQ);
-    long_attr(attn_dbias_long_kernel<true>, 2 * LD_STAGE);
-    attr_set = true;
-  }
   const int qblocks = cdiv(a.Sq, 256);
   const dim3 grid(qblocks * a.H * a.B), blk(512);
-  const size_t lds_b = LB_RING * LB_SLOT_DQ;
-  if (long_tiled(a, a.bias_tiled)) hipLaunchKernelGGL((attn_bwd_dq_long_kernel<true, true>), grid, blk, lds_b, st, a, qblocks);
-  else if (a.bias != nullptr) hipLaunchKernelGGL((attn_bwd_dq_long_kernel<true, false>), grid, blk, lds_b, st, a, qblocks);
-  else hipLaunchKernelGGL((attn_bwd_dq_long_kernel<false, false>), grid, blk, lds_b, st, a, qblocks);
-  int rc = xfm_check_launch("attn_bwd_dq_long");
-  if (rc != XFM_OK || a.dbias == nullptr) return rc;
-  return launch_attn_dbias_blocks(a, st);
+  constexpr int lds_b = LB_RING * LB_SLOT_DQ;
+  if (long_tiled(a, a.bias_tiled)) attn_launch<attn_bwd_dq_long_kernel<true, true>, lds_b>(grid, blk, lds_b, st, a, qblocks);
+  else if (a.bias != nullptr) attn_launch<attn_bwd_dq_long_kernel<true, false>, lds_b>(grid, blk, lds_b, st, a, qblocks);
+  else attn_launch<attn_bwd_dq_long_kernel<false, false>, lds_b>(grid, blk, lds_b, st, a, qblocks);
+  return xfm_check_launch("attn_bwd_dq_long");
 }
 
-// bias gradient (reads the delta a dQ kernel wrote): blocks of 128 x 128, the batch in `slices`
-static int launch_attn_dbias_blocks(const AttnArgs& a, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    long_attr(attn_dbias_long_kernel<true>, 2 * LD_STAGE);
-    attr_set = true;
-  }
-  int rc;
+// bias gradient (reads the delta a dQ kernel wrote): blocks of 128 x 128, the batch in `slices`.  One slice adds to dbias in place;
+// more leave one plane each in a.dbias_ws ([slices, H, Sq, bias_ld]) for dbias_reduce_kernel.
+static int launch_attn_dbias_blocks(const AttnArgs& a, int slices, hipStream_t st) {
   const int qb = cdiv(a.Sq, 128), kb = cdiv(a.Sk, 128);
-  const long per_entry = (long)a.H * a.Sq * a.bias_ld;
-  int slices = dbias_long_slices(qb * kb * a.H, a.B, per_entry * 4);
-  if (slices > 1 && a.dbias_ws == nullptr) slices = 1;  // no plane buffer: one workgroup per block walks the whole batch
   float* planes = slices > 1 ? a.dbias_ws : nullptr;
-  hipLaunchKernelGGL(attn_dbias_long_kernel<true>, dim3(qb * kb * slices * a.H), dim3(512), 2 * LD_STAGE, st, a, qb, kb, slices, planes);
-  rc = xfm_check_launch("attn_dbias_long");
-  if (rc != XFM_OK || slices == 1) return rc;
-  hipLaunchKernelGGL(dbias_reduce_kernel, dim3(cdiv(per_entry / 4, 256)), dim3(256), 0, st, planes, a.dbias, slices, per_entry);
-  return xfm_check_launch("dbias_reduce");
+  attn_launch<attn_dbias_long_kernel<true>, 2 * LD_STAGE>(dim3(qb * kb * slices * a.H), dim3(512), 2 * LD_STAGE, st, a, qb, kb, slices, planes);
+  return xfm_check_launch("attn_dbias_long");
 }
 
 static int launch_attn_bwd_long_dkv(const AttnArgs& a, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    long_attr(attn_bwd_dkv_long_kernel<true, true>, LB_RING * LB_SLOT_DKV);
-    long_attr(attn_bwd_dkv_long_kernel<true, false>, LB_RING * LB_SLOT_DKV);
-    long_attr(attn_bwd_dkv_long_kernel<false, false>, LB_RING * LB_SLOT_DKV);
-    attr_set = true;
-  }
   const int kblocks = cdiv(a.Sk, 256);
   const dim3 grid(kblocks * a.H * a.B), blk(512);
-  const size_t lds_b = LB_RING * LB_SLOT_DKV;
-  if (long_tiled(a, a.bias_t_tiled)) hipLaunchKernelGGL((attn_bwd_dkv_long_kernel<true, true>), grid, blk, lds_b, st, a, kblocks);
-  else if (a.bias != nullptr) hipLaunchKernelGGL((attn_bwd_dkv_long_kernel<true, false>), grid, blk, lds_b, st, a, kblocks);
-  else hipLaunchKernelGGL((attn_bwd_dkv_long_kernel<false, false>), grid, blk, lds_b, st, a, kblocks);
+  constexpr int lds_b = LB_RING * LB_SLOT_DKV;
+  if (long_tiled(a, a.bias_t_tiled)) attn_launch<attn_bwd_dkv_long_kernel<true, true>, lds_b>(grid, blk, lds_b, st, a, kblocks);
+  else if (a.bias != nullptr) attn_launch<attn_bwd_dkv_long_kernel<true, false>, lds_b>(grid, blk, lds_b, st, a, kblocks);
+  else attn_launch<attn_bwd_dkv_long_kernel<false, false>, lds_b>(grid, blk, lds_b, st, a, kblocks);
   return xfm_check_launch("attn_bwd_dkv_long");
 }

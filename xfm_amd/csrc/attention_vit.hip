@@ -1,34 +1,21 @@
 // Self-attention of the 224-px ViT trunk (beit2.py:126-166: S = Sq = Sk = 197, dense rows, relative-position bias, no mask /
 // dropout) as ONE forward kernel and ONE backward kernel whose workgroups walk whole (batch entry, head) problems.  Included by
-// attention.hip (shares its LDS image helpers).
+// attention.hip (the LDS image helpers: attention_common.h).
 //
 // A 197-token problem is small enough to live in one CU: K and V (forward) or Q, dO, K and V (backward) of one (b, h) are 25 KB
-// each.  The general kernels above split a problem over several workgroups -- every one of them re-stages K / V (2.6 x the
+// each.  The general kernels (attention_general.hip) split a problem over several workgroups -- every one of them re-stages K / V (2.6 x the
 // algorithmic bytes beyond L2, profiles/round2_hbm_traffic.json), the backward computes S and dP in two kernels, and the forward
 // rescales an online softmax per 64-key chunk although a whole score row fits in registers.  Here:
 //   * forward (attn_fwd_vit_kernel): 7 waves; a wave owns a 16-query tile against ALL keys (<= 14 key tiles = 56 accumulator VGPRs),
 //     two tiles per item; the scores start from bias / scale as the MFMA accumulator, one row maximum, p = exp2(fma), no rescale;
 //     K / V of the NEXT item land in the second LDS buffers while this one computes;
 //   * backward (attn_bwd_vit3_kernel, opt-in): one pass for dQ, dK, dV, delta and the bias gradient -- see its header for the design and
-//     for why the split dQ + dK/dV kernels of attention.hip remain the default.
+//     for why the split dQ + dK/dV kernels of attention_short.hip remain the default.
 // Items are (head, batch entry) pairs in head-major order, consecutive ones per workgroup: 1536 items = 6 per CU at B = 128.
-#include <type_traits>
 #define VF_MAXT 14                  // 16-row tiles per image (S <= 224)
 #define VF_IMG (VF_MAXT * 2048)     // one [224 x 64] bf16 image
 #define VF_LDS (4 * VF_IMG)         // forward: K | K' | V | V'
 #define VF_NW 7
-
-__device__ __forceinline__ void lds_barrier_v() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-// direct-to-LDS load of one 1-KB piece (8 rows x 128 B): per-lane source address, wave-uniform LDS destination (M0).  Inline asm: see
-// stage_rows in attention.hip (the compiler would drain a visible LDS-DMA before every later LDS read).
-__device__ __forceinline__ void lds_dma16(const char* src, unsigned dst) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory", "m0");
-}
 
 // KTC: the number of 16-row tiles as a compile-time constant (13 = the 224-px ViT: every tile guard folds and the score / product loops
 // become straight-line code the scheduler can pipeline), or 0 = taken from the sequence length at run time (any S <= 224).
@@ -220,7 +207,7 @@ __global__ __launch_bounds__(VF_NW * 64) void attn_fwd_vit_kernel(AttnArgs a, Vi
     asm volatile("" : "+v"(qf[0][0]), "+v"(qf[0][1]), "+v"(qf[1][0]), "+v"(qf[1][1]));
 #pragma unroll
     for (int t = 0; t < VF_MAXT; ++t) asm volatile("" : "+v"(biasA[t]), "+v"(biasB[t]));
-    lds_barrier_v();  // K(it), V(it) have landed; every wave is done with item it-1's buffers
+    lds_barrier();  // K(it), V(it) have landed; every wave is done with item it-1's buffers
     if (more) stage(hn, bn, cur ^ 1);
     run_pass(biasA, qf[0][0], qf[0][1], w, h, b, sK, sV);
     if (w + VF_NW < KT) run_pass(biasB, qf[1][0], qf[1][1], w + VF_NW, h, b, sK, sV);
@@ -228,43 +215,6 @@ __global__ __launch_bounds__(VF_NW * 64) void attn_fwd_vit_kernel(AttnArgs a, Vi
     h = hn;
     b = bn;
   }
-}
-
-// One 64-thread workgroup per (head, tile a, tile b): the tile in the accumulator layout of both kernels (see include/xfm_hip.h).
-__global__ __launch_bounds__(64) void bias_tile_kernel(const float* __restrict__ bias, int S, long ld, float inv_scale, float* __restrict__ tiled,
-                                                       float* __restrict__ tiled_t) {
-  const int T = gridDim.x, a_ = blockIdx.y, b_ = blockIdx.x, h = blockIdx.z;   // a_ in [0, T]: tiled_t has one more key-tile row, all -1e30
-  const int lane = threadIdx.x, lr = lane & 15, lg = lane >> 4;
-  const float* bh = bias + (long)h * S * ld;
-  const long tile = (((long)h * T + a_) * T + b_) * 256 + lane * 4;
-  if (tiled != nullptr && a_ < T) {   // query 16a + lr, keys 16b + 4lg + r
-    const int q = a_ * 16 + lr;
-    f32x4 v;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int k = b_ * 16 + 4 * lg + r;
-      v[r] = k < S ? (q < S ? bh[(long)q * ld + k] * inv_scale : 0.f) : -1.0e30f;
-    }
-    *reinterpret_cast<f32x4*>(tiled + tile) = v;
-  }
-  if (tiled_t != nullptr) {  // key 16a + lr, queries 16b + 4lg + r
-    const int k = a_ * 16 + lr;
-    f32x4 v;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = b_ * 16 + 4 * lg + r;
-      v[r] = k < S ? (q < S ? bh[(long)q * ld + k] * inv_scale : 0.f) : -1.0e30f;
-    }
-    *reinterpret_cast<f32x4*>(tiled_t + (((long)h * (T + 1) + a_) * T + b_) * 256 + lane * 4) = v;
-  }
-}
-
-int xfm_bias_tile_impl(const float* bias, int H, int S, long ld, float scale, float* tiled, float* tiled_t, hipStream_t st) {
-  XFM_REQUIRE(bias != nullptr && H > 0 && S > 0 && ld >= S && scale > 0.f, "bias_tile: bad arguments");
-  XFM_REQUIRE(((uintptr_t)tiled % 16) == 0 && ((uintptr_t)tiled_t % 16) == 0, "bias_tile: outputs must be 16-byte aligned");
-  const int T = cdiv(S, 16);
-  hipLaunchKernelGGL(bias_tile_kernel, dim3(T, T + 1, H), dim3(64), 0, st, bias, S, ld, 1.0f / scale, tiled, tiled_t);
-  return xfm_check_launch("bias_tile");
 }
 
 static bool attn_vit_shape(const AttnArgs& a) {
@@ -275,30 +225,19 @@ static bool attn_vit_shape(const AttnArgs& a) {
          ((uintptr_t)a.bias % 16) == 0;
 }
 
-// (template instantiation + the one-time dynamic-LDS attribute of a kernel: TAG makes one guard per kernel instantiation)
-template <int TAG, typename K>
-static void vit_launch(K kernel, int lds, dim3 grid, dim3 blk, hipStream_t st, const AttnArgs& a, const VitMap& vm) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kernel, grid, blk, lds, st, a, vm);
-}
-
 static int launch_attn_fwd_vit(const AttnArgs& a, hipStream_t st) {
   const VitMap vm = vit_map(a.B, a.H);
   const dim3 grid(vm.grid), blk(VF_NW * 64);
   const bool k13 = cdiv(a.Sq, 16) == 13;
   if (a.bias == nullptr) {
-    if (k13) vit_launch<1>(attn_fwd_vit_kernel<false, 13, false>, VF_LDS, grid, blk, st, a, vm);
-    else vit_launch<2>(attn_fwd_vit_kernel<false, 0, false>, VF_LDS, grid, blk, st, a, vm);
+    if (k13) attn_launch<attn_fwd_vit_kernel<false, 13, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
+    else attn_launch<attn_fwd_vit_kernel<false, 0, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
   } else if (a.bias_tiled != nullptr) {
-    if (k13) vit_launch<3>(attn_fwd_vit_kernel<true, 13, true>, VF_LDS, grid, blk, st, a, vm);
-    else vit_launch<4>(attn_fwd_vit_kernel<true, 0, true>, VF_LDS, grid, blk, st, a, vm);
+    if (k13) attn_launch<attn_fwd_vit_kernel<true, 13, true>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
+    else attn_launch<attn_fwd_vit_kernel<true, 0, true>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
   } else {
-    if (k13) vit_launch<5>(attn_fwd_vit_kernel<true, 13, false>, VF_LDS, grid, blk, st, a, vm);
-    else vit_launch<6>(attn_fwd_vit_kernel<true, 0, false>, VF_LDS, grid, blk, st, a, vm);
+    if (k13) attn_launch<attn_fwd_vit_kernel<true, 13, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
+    else attn_launch<attn_fwd_vit_kernel<true, 0, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
   }
   return xfm_check_launch("attn_fwd_vit");
 }
@@ -466,7 +405,7 @@ __global__ __launch_bounds__(512) void attn_bwd_vit3_kernel(AttnArgs a, VitMap v
   if (w == 7) stage_pair(h, b, 0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (w == 7) publish_stats(h, b, 0, 0);
-  lds_barrier_v();
+  lds_barrier();
 
   f32x4 dKa[2][4], dVa[2][4];
 #pragma unroll
@@ -620,7 +559,7 @@ __global__ __launch_bounds__(512) void attn_bwd_vit3_kernel(AttnArgs a, VitMap v
       // ---------------- dQ of the previous pair (exchange buffer slot ^ 1): one unit per wave
       if (p > 0) dq_unit(h, b, p - 1, slot ^ 1, par, w);
       else if (have_prev) dq_unit(hp, bp, NP - 1, slot ^ 1, par ^ 1, w);
-      lds_barrier_v();
+      lds_barrier();
     }
     // ---- dK, dV of this wave's keys; the bias gradient leaves when the head changes
     if (owner) {
@@ -649,7 +588,7 @@ __global__ __launch_bounds__(512) void attn_bwd_vit3_kernel(AttnArgs a, VitMap v
       flush(h, par ^ 1);
 #pragma unroll
       for (int i = 0; i < (DBIAS ? KT : 1); ++i) dsacc[i][0] = dsacc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      lds_barrier_v();
+      lds_barrier();
     }
     h = hn;
     b = bn;
@@ -660,8 +599,8 @@ __global__ __launch_bounds__(512) void attn_bwd_vit3_kernel(AttnArgs a, VitMap v
   flush(hp, last_par ^ 1);
 }
 
-static bool attn_vit3_shape(const AttnArgs& a) {
-  const int mode = xfm_env_int("XFM_ATTN_VIT_BWD", 0);   // (read per call: the tests switch it inside one process)
+// mode: XFM_ATTN_VIT_BWD (0 = the split pair of attention_short.hip, the default)
+static bool attn_vit3_shape(const AttnArgs& a, int mode) {
   return mode != 0 && attn_vit_shape(a) && cdiv(a.Sq, 16) == V3_KT && a.bwd_phase == 0 && a.o != nullptr && a.o_lo == nullptr &&
          (a.bias == nullptr || a.bias_t_tiled != nullptr) && (a.dbias == nullptr || a.bias != nullptr) &&
          ((uintptr_t)a.dout % 16) == 0 && ((uintptr_t)a.o % 16) == 0 && a.o_rs % 8 == 0;
@@ -669,8 +608,9 @@ static bool attn_vit3_shape(const AttnArgs& a) {
 
 static int launch_attn_bwd_vit3(const AttnArgs& a, hipStream_t st) {
   const VitMap vm = vit_map(a.B, a.H);
-  if (a.bias != nullptr && a.dbias != nullptr) vit_launch<7>(attn_bwd_vit3_kernel<true, true>, V3_LDS, dim3(vm.grid), dim3(512), st, a, vm);
-  else if (a.bias != nullptr) vit_launch<9>(attn_bwd_vit3_kernel<true, false>, V3_LDS, dim3(vm.grid), dim3(512), st, a, vm);
-  else vit_launch<8>(attn_bwd_vit3_kernel<false, false>, V3_LDS, dim3(vm.grid), dim3(512), st, a, vm);
+  const dim3 grid(vm.grid), blk(512);
+  if (a.bias != nullptr && a.dbias != nullptr) attn_launch<attn_bwd_vit3_kernel<true, true>, V3_LDS>(grid, blk, V3_LDS, st, a, vm);
+  else if (a.bias != nullptr) attn_launch<attn_bwd_vit3_kernel<true, false>, V3_LDS>(grid, blk, V3_LDS, st, a, vm);
+  else attn_launch<attn_bwd_vit3_kernel<false, false>, V3_LDS>(grid, blk, V3_LDS, st, a, vm);
   return xfm_check_launch("attn_bwd_vit3");
 }

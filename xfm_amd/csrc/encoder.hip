@@ -1,5 +1,5 @@
 // One RobertaLayer per call (xroberta.py:405-473 of the reference): the launch sequence of the layer's forward and of its backward,
-// on the native side.  No new arithmetic lives here -- every step is one of the kernels of gemm.hip / attention.hip / layernorm.hip,
+// on the native side.  No new arithmetic lives here -- every step is one of the kernels of gemm.hip / attention*.hip / layernorm.hip,
 // called through the same *_impl entry points as the one-kernel C ABI -- what this file owns is ORDER and STREAMS:
 //
 //   forward   qkv GEMM -> self-attention -> output GEMM -> dropout+residual+LayerNorm

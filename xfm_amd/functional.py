@@ -93,7 +93,7 @@ def gemm_nt_ksplit(a, b, n=None, bias=None, out_dtype=BF16):
 def deterministic():
     """XFM_DETERMINISTIC=1: the reductions that by default still end in float atomics because their ordered form costs a launch or a pass
     take the ordered form (read per call, like the library's own switch): the bias column sums that ride on the M-split weight-gradient
-    GEMMs (here), the bias gradient of the short attention backward (per-slice planes, csrc/attention.hip), the embedding gradients
+    GEMMs (here), the bias gradient of the short attention backward (per-slice planes, csrc/attention_short.hip), the embedding gradients
     (sorted segment sums, embed_ln_bwd).  Every other reduction of the step is ordered unconditionally (tools/bit_repro.py)."""
     return os.environ.get("XFM_DETERMINISTIC", "0") not in ("", "0")
 
