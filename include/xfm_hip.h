@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 9
+#define XFM_ABI_VERSION 10
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -442,6 +442,42 @@ int xfm_ce_fwd(const float* logits, long ld, int R, int V, const int64_t* labels
 /* dlogits = (softmax - onehot) * scale[0]  (per_row_scale = 0: mean / sum reductions) or * scale[row] (reduction 'none'). */
 int xfm_ce_bwd(const float* logits, long ld, int R, int V, const int64_t* labels, const float* lse, const float* scale,
                int per_row_scale, xfm_bf16* dlogits, long ldd, void* stream);
+
+/* ---- Cross-entropy against a target row that is not one-hot: loss_r = -sum_c t_c log_softmax(x)_c (ABI 10) ---------------------------
+ * Logits, lse, scale and dlogits as in xfm_ce_fwd/bwd: fp32 [R, ld] with V live columns (ld % 4 == 0 and a 16-byte aligned base unless
+ * V < 4; columns [V, ld) are never read), bf16 dlogits [R, ldd] (ldd % 8 == 0), zero in columns [V, ldd) and in ignored rows,
+ * scale[0] or scale[row].  The forward reads every row once (online max / sum-exp), one workgroup per row.
+ *
+ * LABEL form -- the row is described, not materialised: t_c = off + (on - off) (lam_r [c == a_r] + (1 - lam_r) [c == b_r]);
+ * labels_a int64 [R] (outside [0, V), e.g. -100: the row is ignored -- loss 0, gradient 0), labels_b int64 [R] or NULL (b = a; a live
+ * row's b must lie in [0, V), else the row is ignored too), lam fp32 [R] or NULL (1).  With St = V off + (on - off):
+ *   loss_r = St lse_r - off sum_c x_c - (on - off) (lam x_a + (1 - lam) x_b),      dlogits = (St softmax - t) scale.
+ * Replaces: LabelSmoothSoftmaxCEV1 (xbert.py:1190-1229, used at :1346-1347; Captioning.yaml:28): on = 1 - s, off = s / V;
+ * timm LabelSmoothingCrossEntropy (Imagenet.py:608-609) = F.cross_entropy(label_smoothing = s): on = 1 - s + s / V, off = s / V;
+ * SoftTargetCrossEntropy on Mixup's two-label targets (Imagenet.py:605-607) without the dense target.  on = 1, off = 0, lam = NULL is
+ * xfm_ce_fwd/bwd up to the accumulation order. */
+int xfm_ce_smooth_fwd(const float* logits, long ld, int R, int V, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      float on, float off, float* lse, float* loss, void* stream);
+int xfm_ce_smooth_bwd(const float* logits, long ld, int R, int V, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      float on, float off, const float* lse, const float* scale, int per_row_scale, xfm_bf16* dlogits, long ldd,
+                      void* stream);
+/* DENSE form -- timm SoftTargetCrossEntropy (Imagenet.py:605-607: sum(-target * log_softmax(x), dim=-1)): target fp32 [R, ldt] (the
+ * stride rules of the logits), any non-negative row, any row sum.  loss_r = lse_r sum_c t_c - sum_c t_c x_c; the forward reads logits
+ * and target once each and stores lse [R] and tsum [R] (= sum_c t_c) for the backward: dlogits = (softmax tsum - t) scale. */
+int xfm_ce_soft_fwd(const float* logits, long ld, const float* target, long ldt, int R, int V, float* lse, float* tsum, float* loss,
+                    void* stream);
+int xfm_ce_soft_bwd(const float* logits, long ld, const float* target, long ldt, int R, int V, const float* lse, const float* tsum,
+                    const float* scale, int per_row_scale, xfm_bf16* dlogits, long ldd, void* stream);
+
+/* ---- Device Mixup / CutMix (timm Mixup._mix_batch / _mix_elem and mixup_target as called at Imagenet.py:468-469; ABI 10) -------------
+ * xfm_mixup: fp32 images [B, C, H, W], B even, mixed IN PLACE: row i against the original row j = B - 1 - i, with the per-row device
+ * arrays lam fp32 [B] and box int32 [B, 4] = (yl, yh, xl, xh).  lam_i == 1: row i is left alone; an empty box (yh <= yl or xh <= xl):
+ * x_i <- lam_i x_i + (1 - lam_i) x_j; otherwise the pixels inside the box are copied bit for bit from x_j and the rest is untouched.
+ * One pass (each element of the batch is read once and written at most once) in place of flip, mul_, mul_, add_.
+ * xfm_mixup_target: out fp32 [B, ldo] (ldo >= num_classes; columns past num_classes are zeroed),
+ * out[i] = lam_i onehot_s(labels_i) + (1 - lam_i) onehot_s(labels_{B-1-i}), off = s / num_classes, on = 1 - s + off. */
+int xfm_mixup(float* x, int B, int C, int H, int W, const float* lam, const int* box, void* stream);
+int xfm_mixup_target(const int64_t* labels, const float* lam, int B, int num_classes, float smoothing, float* out, long ldo, void* stream);
 
 /* ---- Flat-arena optimiser step (optim.py:4-50 + clip, apex_ddp_accelerator.py:100-110) --------------------------- */
 typedef struct {

@@ -272,15 +272,17 @@ BERT_BASE_CONFIG = dict(vocab_size=30522, hidden_size=768, num_hidden_layers=12,
                         pad_token_id=0)
 
 
-def gen_bert_causal_lm(layers=2, B=6, L=9, S=30):
+def gen_bert_causal_lm(layers=2, B=6, L=9, S=30, label_smoothing=0.0):
     """The answer decoder of a bert-named VQA model (model_generation.py:52-54 -> xbert.BertLMHeadModel, xbert.py:1235-1347): BERT
     embeddings, causal self mask, cross-attention in every layer, BertOnlyMLMHead, shifted CE with reduction='none', per-sequence
-    weighted sum -- the same case as causal_lm_2L on the xbert stack ([PAD] = 0)."""
+    weighted sum -- the same case as causal_lm_2L on the xbert stack ([PAD] = 0).
+    label_smoothing > 0 (Captioning.yaml:28; xbert.py:1346-1347 -> LabelSmoothSoftmaxCEV1): the same inputs into
+    bert_causal_lm_smooth_2L, which also holds the reduction='mean' loss."""
     from models.xbert import BertConfig, BertLMHeadModel
     torch.manual_seed(0)
     cfg = BertConfig(**BERT_BASE_CONFIG)
     cfg.num_hidden_layers, cfg.fusion_layer, cfg.encoder_width = layers, 0, 768
-    m = BertLMHeadModel(cfg)
+    m = BertLMHeadModel(cfg, label_smoothing=label_smoothing) if label_smoothing > 0 else BertLMHeadModel(cfg)
     load_formula(m)
     m.eval()
     b = syn.pretrain_batch(B, seed=13, with_image=False, vocab=30522)
@@ -305,8 +307,15 @@ def gen_bert_causal_lm(layers=2, B=6, L=9, S=30):
     loss.backward()
     grads_of(m, out, "grad")
     pack("grad_in/question_states", enc.grad, out)
-    save(f"bert_causal_lm_{layers}L", out, {"spec": spec_of(m), "B": B, "L": L, "S": S, "layers": layers,
-                                            "ids": ids.tolist(), "atts": atts.tolist(), "enc_atts": enc_atts.tolist()})
+    meta = {"spec": spec_of(m), "B": B, "L": L, "S": S, "layers": layers, "ids": ids.tolist(), "atts": atts.tolist(),
+            "enc_atts": enc_atts.tolist()}
+    if label_smoothing > 0:
+        with torch.no_grad():
+            mean = m(ids, attention_mask=atts, encoder_hidden_states=enc, encoder_attention_mask=enc_atts,
+                     labels=ids.masked_fill(ids == 0, -100), return_dict=True, reduction="mean")
+        out["loss_mean"] = np.asarray(float(mean.loss))
+        meta["label_smoothing"] = label_smoothing
+    save(f"bert_causal_lm_{'smooth_' if label_smoothing > 0 else ''}{layers}L", out, meta)
 
 
 def gen_xbert(layers=2, B=4):
@@ -1030,7 +1039,8 @@ def main():
     torch.set_num_threads(int(os.environ.get("GEN_THREADS", "8")))
     ref_shim.install()
     jobs = {"beit": lambda: gen_beit(2), "roberta_text": lambda: gen_roberta_text(2), "fusion": lambda: gen_fusion(2),
-            "pretrain_small": lambda: gen_pretrain("pretrain_small", 2, 2), "causal_lm": lambda: gen_causal_lm(2), "bert_causal_lm": lambda: gen_bert_causal_lm(2), "xbert": lambda: gen_xbert(2), "vit": lambda: gen_vit(2), "retrieval": lambda: gen_retrieval(), "checkpoint": lambda: gen_checkpoint(), "classification": lambda: gen_classification(), "vqa": gen_vqa, "nlvr": gen_nlvr, "retrieval_eval": gen_retrieval_eval, "harness": gen_harness, "checkpoint_vqa": gen_checkpoint_vqa, "grounding": gen_grounding, "grounding_domain": gen_grounding_domain,
+            "pretrain_small": lambda: gen_pretrain("pretrain_small", 2, 2), "causal_lm": lambda: gen_causal_lm(2), "bert_causal_lm": lambda: gen_bert_causal_lm(2),
+            "bert_causal_lm_smooth": lambda: gen_bert_causal_lm(2, label_smoothing=0.1), "xbert": lambda: gen_xbert(2), "vit": lambda: gen_vit(2), "retrieval": lambda: gen_retrieval(), "checkpoint": lambda: gen_checkpoint(), "classification": lambda: gen_classification(), "vqa": gen_vqa, "nlvr": gen_nlvr, "retrieval_eval": gen_retrieval_eval, "harness": gen_harness, "checkpoint_vqa": gen_checkpoint_vqa, "grounding": gen_grounding, "grounding_domain": gen_grounding_domain,
             "retrieval_384": lambda: gen_retrieval(B=8, res=384, T=40, name="retrieval_384"),
             "vqa_480": lambda: gen_vqa(res=480, name="vqa_480")}
     cfg_jobs = {"retrieval_cfg": gen_retrieval_cfg, "vqa_cfg": gen_vqa_cfg, "pretrain_cfg": gen_pretrain_cfg, "imagenet_cfg": gen_imagenet_cfg}   # config-shape fixtures: minutes of CPU each, only on request

@@ -36,6 +36,7 @@ int xfm_cu_count() {
 #include "elementwise.hip"
 #include "encoder.hip"
 #include "losses.hip"
+#include "losses_soft.hip"
 #include "dp.hip"
 
 #define ST(s) ((hipStream_t)(s))
@@ -271,6 +272,36 @@ int xfm_ce_bwd(const float* logits, long ld, int R, int V, const int64_t* labels
                int per_row_scale, xfm_bf16* dlogits, long ldd, void* stream) {
   XFM_REQUIRE(logits && labels && lse && scale && dlogits, "ce_bwd: null operand");
   return xfm_ce_bwd_impl(logits, ld, R, V, labels, lse, scale, per_row_scale, dlogits, ldd, ST(stream));
+}
+
+int xfm_ce_smooth_fwd(const float* logits, long ld, int R, int V, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      float on, float off, float* lse, float* loss, void* stream) {
+  XFM_REQUIRE(logits && labels_a && lse && loss, "ce_smooth_fwd: null operand");
+  return xfm_ce_smooth_fwd_impl(logits, ld, R, V, labels_a, labels_b, lam, on, off, lse, loss, ST(stream));
+}
+int xfm_ce_smooth_bwd(const float* logits, long ld, int R, int V, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      float on, float off, const float* lse, const float* scale, int per_row_scale, xfm_bf16* dlogits, long ldd,
+                      void* stream) {
+  XFM_REQUIRE(logits && labels_a && lse && scale && dlogits, "ce_smooth_bwd: null operand");
+  return xfm_ce_smooth_bwd_impl(logits, ld, R, V, labels_a, labels_b, lam, on, off, lse, scale, per_row_scale, dlogits, ldd, ST(stream));
+}
+int xfm_ce_soft_fwd(const float* logits, long ld, const float* target, long ldt, int R, int V, float* lse, float* tsum, float* loss,
+                    void* stream) {
+  XFM_REQUIRE(logits && target && lse && tsum && loss, "ce_soft_fwd: null operand");
+  return xfm_ce_soft_fwd_impl(logits, ld, target, ldt, R, V, lse, tsum, loss, ST(stream));
+}
+int xfm_ce_soft_bwd(const float* logits, long ld, const float* target, long ldt, int R, int V, const float* lse, const float* tsum,
+                    const float* scale, int per_row_scale, xfm_bf16* dlogits, long ldd, void* stream) {
+  XFM_REQUIRE(logits && target && lse && tsum && scale && dlogits, "ce_soft_bwd: null operand");
+  return xfm_ce_soft_bwd_impl(logits, ld, target, ldt, R, V, lse, tsum, scale, per_row_scale, dlogits, ldd, ST(stream));
+}
+int xfm_mixup(float* x, int B, int C, int H, int W, const float* lam, const int* box, void* stream) {
+  XFM_REQUIRE(x && lam && box, "mixup: null operand");
+  return xfm_mixup_impl(x, B, C, H, W, lam, box, ST(stream));
+}
+int xfm_mixup_target(const int64_t* labels, const float* lam, int B, int num_classes, float smoothing, float* out, long ldo, void* stream) {
+  XFM_REQUIRE(labels && lam && out, "mixup_target: null operand");
+  return xfm_mixup_target_impl(labels, lam, B, num_classes, smoothing, out, ldo, ST(stream));
 }
 
 int xfm_adamw(const xfm_adamw_args* a, void* stream) {

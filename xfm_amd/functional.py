@@ -760,6 +760,83 @@ def ce_bwd(logits, V, labels, lse, scale, ldd):
     return d
 
 
+def _ce_rows(logits, V):
+    _dev(logits)
+    assert logits.dtype == F32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[1] >= V
+    return logits.shape[0]
+
+
+def ce_smooth_fwd(logits, V, labels_a, on, off, labels_b=None, lam=None):
+    """Label-form soft CE (xfm_ce_smooth_fwd): the target row off + (on - off) (lam [c == a] + (1 - lam) [c == b]) is never built.
+    logits fp32 [R, ld>=V]; labels_a / labels_b int64 [R] (a of -100 ignores the row; b None = a); lam fp32 [R] or None (1)
+    -> (lse [R], loss_rows [R])."""
+    R = _ce_rows(logits, V)
+    assert labels_a.dtype == torch.int64 and labels_a.numel() == R and (labels_b is None or (labels_b.dtype == torch.int64 and labels_b.numel() == R))
+    assert lam is None or (lam.dtype == F32 and lam.numel() == R)
+    lse = torch.empty(R, dtype=F32, device=logits.device)
+    loss = torch.empty(R, dtype=F32, device=logits.device)
+    check(_lib.load().xfm_ce_smooth_fwd(logits.data_ptr(), logits.stride(0), R, V, labels_a.data_ptr(), _ptr(labels_b), _ptr(lam), float(on),
+                                        float(off), lse.data_ptr(), loss.data_ptr(), _stream()), "ce_smooth_fwd")
+    return lse, loss
+
+
+def ce_smooth_bwd(logits, V, labels_a, on, off, lse, scale, ldd, labels_b=None, lam=None):
+    """-> dlogits bf16 [R, ldd] = ((V off + on - off) softmax - target row) * scale; scale fp32 [1] or [R] as in ce_bwd."""
+    R = _ce_rows(logits, V)
+    d = torch.empty((R, ldd), dtype=BF16, device=logits.device)
+    assert scale.dtype == F32 and scale.numel() in (1, R)
+    check(_lib.load().xfm_ce_smooth_bwd(logits.data_ptr(), logits.stride(0), R, V, labels_a.data_ptr(), _ptr(labels_b), _ptr(lam), float(on),
+                                        float(off), lse.data_ptr(), scale.data_ptr(), int(scale.numel() == R and R > 1), d.data_ptr(), ldd,
+                                        _stream()), "ce_smooth_bwd")
+    return d
+
+
+def ce_soft_fwd(logits, V, target):
+    """Dense soft-target CE (xfm_ce_soft_fwd): logits fp32 [R, ld>=V], target fp32 [R, ldt>=V] (non-negative, any row sum)
+    -> (lse [R], tsum [R] = the rows' target sums, loss_rows [R])."""
+    R = _ce_rows(logits, V)
+    assert target.dtype == F32 and target.dim() == 2 and target.stride(1) == 1 and target.shape[0] == R and target.shape[1] >= V
+    lse, tsum, loss = (torch.empty(R, dtype=F32, device=logits.device) for _ in range(3))
+    check(_lib.load().xfm_ce_soft_fwd(logits.data_ptr(), logits.stride(0), target.data_ptr(), target.stride(0), R, V, lse.data_ptr(),
+                                      tsum.data_ptr(), loss.data_ptr(), _stream()), "ce_soft_fwd")
+    return lse, tsum, loss
+
+
+def ce_soft_bwd(logits, V, target, lse, tsum, scale, ldd):
+    """-> dlogits bf16 [R, ldd] = (softmax * tsum - target) * scale; scale fp32 [1] or [R] as in ce_bwd."""
+    R = _ce_rows(logits, V)
+    d = torch.empty((R, ldd), dtype=BF16, device=logits.device)
+    assert scale.dtype == F32 and scale.numel() in (1, R)
+    check(_lib.load().xfm_ce_soft_bwd(logits.data_ptr(), logits.stride(0), target.data_ptr(), target.stride(0), R, V, lse.data_ptr(),
+                                      tsum.data_ptr(), scale.data_ptr(), int(scale.numel() == R and R > 1), d.data_ptr(), ldd, _stream()),
+          "ce_soft_bwd")
+    return d
+
+
+def mixup_(x, lam, box):
+    """In-place batch mix (xfm_mixup): x fp32 [B, C, H, W] contiguous, B even; row i against the original row B - 1 - i with lam fp32 [B]
+    and box int32 [B, 4] = (yl, yh, xl, xh) on the device (lam 1: untouched; empty box: mixup; else CutMix inside the box) -> x."""
+    _dev(x)
+    assert x.dtype == F32 and x.dim() == 4 and x.is_contiguous()
+    B, C, H, W = x.shape
+    assert lam.dtype == F32 and lam.numel() == B and lam.is_contiguous() and box.dtype == torch.int32 and box.shape == (B, 4) and box.is_contiguous()
+    check(_lib.load().xfm_mixup(x.data_ptr(), B, C, H, W, lam.data_ptr(), box.data_ptr(), _stream()), "mixup")
+    return x
+
+
+def mixup_target(labels, lam, num_classes, smoothing=0.0, ld=None):
+    """Dense mixed target (xfm_mixup_target): labels int64 [B], lam fp32 [B] -> fp32 [B, num_classes] (a view of a [B, ld] buffer whose
+    padding columns are zero when ld is given)."""
+    _dev(labels)
+    B = labels.numel()
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and lam.dtype == F32 and lam.numel() == B and lam.is_contiguous()
+    ld = num_classes if ld is None else ld
+    out = torch.empty((B, ld), dtype=F32, device=labels.device)
+    check(_lib.load().xfm_mixup_target(labels.data_ptr(), lam.data_ptr(), B, num_classes, float(smoothing), out.data_ptr(), ld, _stream()),
+          "mixup_target")
+    return out[:, :num_classes]
+
+
 def sumsq(x, out):
     ws = workspace(4096, x.device)  # XFM_SUMSQ_WORKSPACE_FLOATS block partials
     check(_lib.load().xfm_sumsq(x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), _stream()), "sumsq")

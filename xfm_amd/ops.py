@@ -186,10 +186,12 @@ VOCAB_LD = 64  # logits / dlogits row stride is padded to a multiple of this (th
 
 class _LMHeadCEFn(torch.autograd.Function):
     """RobertaLMHead (dense -> GELU -> LayerNorm -> decoder, xroberta.py:1325-1333) fused with the vocabulary
-    cross-entropy (ignore_index=-100, xroberta.py:1296-1297).  Returns (reduced loss, fp32 logits view)."""
+    cross-entropy (ignore_index=-100, xroberta.py:1296-1297).  Returns (reduced loss, fp32 logits view).
+    label_smoothing > 0: LabelSmoothSoftmaxCEV1 (xbert.py:1190-1229) through the label-form kernels -- the target row is 1 - s at the
+    label and s / V elsewhere (it sums to 1 - s / V), ignored rows contribute 0, 'mean' divides by the valid count."""
 
     @staticmethod
-    def forward(ctx, x, head, labels, reduction):
+    def forward(ctx, x, head, labels, reduction, label_smoothing=0.0):
         R, D = x.shape
         sd, sv = head._slot_dense, head._slot_decoder
         V = sv.N
@@ -201,10 +203,13 @@ class _LMHeadCEFn(torch.autograd.Function):
         # 148 us for the plan's 256 x 128 ring at 960 rows; below ~512 rows the plan's choice stands)
         Fx.gemm_nt(y, sv.wb, sv.b, epi=Fx.EPI_F32, out=logits, n=V, tile_hint=5 if R >= 512 else 0)
         labels = labels.reshape(-1).contiguous()
-        lse, loss_rows = Fx.ce_fwd(logits, V, labels)
+        if label_smoothing > 0:
+            lse, loss_rows = Fx.ce_smooth_fwd(logits, V, labels, 1.0 - label_smoothing, label_smoothing / V)
+        else:
+            lse, loss_rows = Fx.ce_fwd(logits, V, labels)
         nvalid = (labels != -100).sum().clamp(min=1).to(F32)
         ctx.saved = (x, hact, u, y, mean, rstd, logits, labels, lse, nvalid)
-        ctx.head, ctx.reduction = head, reduction
+        ctx.head, ctx.reduction, ctx.label_smoothing = head, reduction, label_smoothing
         ctx.mark_non_differentiable(logits)
         if reduction == "mean":
             return loss_rows.sum() / nvalid, logits
@@ -222,7 +227,11 @@ class _LMHeadCEFn(torch.autograd.Function):
             scale = g.reshape(-1).to(F32).contiguous()  # per-row upstream gradients
         else:
             scale = (g / nvalid if ctx.reduction == "mean" else g).reshape(1).to(F32).contiguous()
-        dlogits = Fx.ce_bwd(logits, V, labels, lse, scale, logits.shape[1])
+        if ctx.label_smoothing > 0:
+            s = ctx.label_smoothing
+            dlogits = Fx.ce_smooth_bwd(logits, V, labels, 1.0 - s, s / V, lse, scale, logits.shape[1])
+        else:
+            dlogits = Fx.ce_bwd(logits, V, labels, lse, scale, logits.shape[1])
         # the two weight gradients (the 50265 x 768 one takes 310 us) go to the second stream and re-join at the end of the backward
         # pass: they run under the fusion tower's latency-bound activation-gradient chain instead of in front of it
         from .xroberta import _WgradStream
@@ -239,11 +248,11 @@ class _LMHeadCEFn(torch.autograd.Function):
         wg.gemm_tn(du, x, sd.dw, dbias=sd.db)
         dx = Fx.gemm_nt(du, sd.wt, n=sd.K)
         wg.join_at_end()
-        return dx, None, None, None
+        return dx, None, None, None, None
 
 
-def lm_head_ce(x, head, labels, reduction="mean"):
-    return _LMHeadCEFn.apply(x.contiguous(), head, labels, reduction)
+def lm_head_ce(x, head, labels, reduction="mean", label_smoothing=0.0):
+    return _LMHeadCEFn.apply(x.contiguous(), head, labels, reduction, float(label_smoothing))
 
 
 def lm_head_logits(x, head):

@@ -142,14 +142,12 @@ class BertForMaskedLM(OwnsArena, nn.Module):
 class BertLMHeadModel(OwnsArena, nn.Module):
     """Causal decoder with cross-attention to encoder states on the BERT-flavoured stack (xbert.py:1235-1347): what
     model_generation.py:54 builds as `text_decoder` for a bert-named text encoder.  Same fused stack and LM-head node as
-    xroberta.RobertaForCausalLM; the state_dict keys are the reference's (`bert.*`, `cls.predictions.*`).  Label smoothing
-    (xbert.py:1336-1337, LabelSmoothSoftmaxCEV1) is used by no XFM task model: > 0 raises.  Generation (beam search, past_key_values)
-    is outside the hot-path scope, as for the RoBERTa decoder."""
+    xroberta.RobertaForCausalLM; the state_dict keys are the reference's (`bert.*`, `cls.predictions.*`).  label_smoothing > 0
+    (xbert.py:1346-1347, LabelSmoothSoftmaxCEV1 at :1190-1229; Captioning.yaml:28 sets 0.1) runs the label-form soft CE kernels inside
+    the same LM-head node.  Generation (beam search, past_key_values) is outside the hot-path scope, as for the RoBERTa decoder."""
 
     def __init__(self, config, label_smoothing=0.0):
         super().__init__()
-        if label_smoothing > 0:
-            raise NotImplementedError("label smoothing (xbert.py:1336-1337) is not used on the XFM path")
         self.config = config
         self.bert = BertModel(config, add_pooling_layer=False)
         self.cls = BertOnlyMLMHead(config)
@@ -192,7 +190,7 @@ class BertLMHeadModel(OwnsArena, nn.Module):
             return SimpleNamespace(loss=None, logits=logits, hidden_states=seq, past_key_values=None, attentions=None,
                                    cross_attentions=None)
         shifted, lab = seq[:, :-1, :], labels[:, 1:]   # next-token prediction (xbert.py:1331-1333)
-        loss, logits = lm_head_ce(shifted.reshape(-1, seq.shape[-1]), head, lab.reshape(-1), reduction)
+        loss, logits = lm_head_ce(shifted.reshape(-1, seq.shape[-1]), head, lab.reshape(-1), reduction, self.label_smoothing)
         if reduction == 'none':
             loss = loss.view(B, -1).sum(1)
         return SimpleNamespace(loss=loss, logits=logits[:, :V].view(B, T - 1, V), hidden_states=seq, past_key_values=None,

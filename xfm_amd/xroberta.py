@@ -1286,13 +1286,16 @@ class RobertaForMaskedLM(OwnsArena, nn.Module):
 class RobertaForCausalLM(OwnsArena, nn.Module):
     """Causal decoder with cross-attention to encoder states (the VQA answer decoder): mirrors models/xroberta.py:963-1153 --
     `roberta` + `lm_head`, causal self-attention mask, next-token shift, `reduction='none'` CE summed per sequence
-    (:1107-1114)."""
+    (:1107-1114).  `label_smoothing` is the keyword model_generation.py:275 passes to this class; the reference's own class does not
+    take it (only its BERT sibling does, xbert.py:1240), so that call raises there.  Here it has the sibling's meaning
+    (LabelSmoothSoftmaxCEV1, xbert.py:1190-1229: 1 - s at the label, s / V elsewhere); 0 is the plain CE, kernel for kernel."""
 
-    def __init__(self, config):
+    def __init__(self, config, label_smoothing=0.0):
         super().__init__()
         self.config = config
         self.roberta = RobertaModel(config, add_pooling_layer=False)
         self.lm_head = RobertaLMHead(config)
+        self.label_smoothing = label_smoothing
         self._arena = None
 
     def linear_slots(self, prefix=""):
@@ -1327,7 +1330,7 @@ class RobertaForCausalLM(OwnsArena, nn.Module):
             return SimpleNamespace(loss=None, logits=logits, hidden_states=seq, past_key_values=None, attentions=None,
                                    cross_attentions=None)
         shifted, lab = seq[:, :-1, :], labels[:, 1:]
-        loss, logits = lm_head_ce(shifted.reshape(-1, seq.shape[-1]), self.lm_head, lab.reshape(-1), reduction)
+        loss, logits = lm_head_ce(shifted.reshape(-1, seq.shape[-1]), self.lm_head, lab.reshape(-1), reduction, self.label_smoothing)
         if reduction == 'none':
             loss = loss.view(B, -1).sum(1)
         return SimpleNamespace(loss=loss, logits=logits[:, :V].view(B, T - 1, V), hidden_states=seq, past_key_values=None,
