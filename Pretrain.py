@@ -46,6 +46,26 @@ class SyntheticLoader:
             yield self.batches[i % len(self.batches)]
 
 
+class SyntheticRegionLoader:
+    """`steps` region batches in the tuple layout run_region_iter unpacks (xfm_amd.synthetic.region_batch), sized by the config's
+    `regions:` section (batch_size, max_images, max_regions)."""
+
+    def __init__(self, steps, regions, seed, image_res=224, patch_size=16, max_tokens=30, max_masks=15, vocab=None, pool=4):
+        from xfm_amd import synthetic as syn
+        kw = {} if vocab is None else {"vocab": vocab}
+        self.steps = steps
+        self.batches = [syn.region_batch(regions["batch_size"], regions["max_images"], regions["max_regions"], seed=seed + 7919 * k,
+                                         image_res=image_res, patch_size=patch_size, max_tokens=max_tokens, max_masks=max_masks, **kw)
+                        for k in range(min(pool, steps))]
+
+    def __len__(self):
+        return self.steps
+
+    def __iter__(self):
+        for i in range(self.steps):
+            yield self.batches[i % len(self.batches)]
+
+
 class Checkpointer:
     """utils/checkpointer.py:20-47, local paths only."""
 
@@ -102,6 +122,10 @@ def main(args, config):
         text_loader = SyntheticLoader(steps, t.get("batch_size", config["batch_size"]), seed + 1, with_image=False,
                                       max_tokens=min(t.get("max_tokens", 30), 128), max_masks=t.get("max_masks", 15), vocab=vocab,
                                       image_res=config["image_res"])
+    region_loader = None
+    if config.get("regions"):  # stands in for train_file_regions (run_region_iter, before every image step)
+        region_loader = SyntheticRegionLoader(steps, config["regions"], seed + 2, patch_size=config["patch_size"], **mk)
+        config.setdefault("calc_image_bbox_loss", False)
 
     print("Creating model XFM", flush=True)
     model = XFM(config=config).to(device)
@@ -128,7 +152,7 @@ def main(args, config):
 
     start_time = time.time()
     print("Start training", flush=True)
-    stats = PL.train(model, image_loader, (None, None, None, None, text_loader), optimizer, (start_epoch, config["schedular"]["epochs"]),
+    stats = PL.train(model, image_loader, (None, None, None, region_loader, text_loader), optimizer, (start_epoch, config["schedular"]["epochs"]),
                      device, lr_scheduler, config, accelerator, checkpointer, world_size=world_size,
                      print_freq=config.get("print_freq", 50), log=log)
     torch.cuda.synchronize()

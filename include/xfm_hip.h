@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 10
+#define XFM_ABI_VERSION 11
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -478,6 +478,28 @@ int xfm_ce_soft_bwd(const float* logits, long ld, const float* target, long ldt,
  * out[i] = lam_i onehot_s(labels_i) + (1 - lam_i) onehot_s(labels_{B-1-i}), off = s / num_classes, on = 1 - s + off. */
 int xfm_mixup(float* x, int B, int C, int H, int W, const float* lam, const int* box, void* stream);
 int xfm_mixup_target(const int64_t* labels, const float* lam, int B, int num_classes, float smoothing, float* out, long ldo, void* stream);
+
+/* ---- Region pre-training step (Pretrain.py:94-121 run_region_iter; ABI 11) -------------------------------------------------------------
+ * Region pooling (the vision tower's region call form, beit2.py:467-475): full bf16 [n_img, 1 + P, D] is the tower's normalised
+ * output, idx int32 [bs] names the image of every sample, atts bytes [bs, P] are the patch columns of image_atts (0 / 1).
+ *   fwd: out bf16 [bs, 1 + P, D]: rows 1..P of sample s = the patch rows of image idx[s], bit for bit; row 0 = sum_p atts[s, p]
+ *        full[idx[s], 1 + p, :] / sum_p atts[s, p], fp32 sums rounded once.  wsum fp32 [bs] = sum_p atts[s, p], for the backward.  One
+ *        pass over the gathered rows.  (A sample whose mask is all zero gets the reference's non-finite row 0.)
+ *   bwd: dfull bf16 [n_img, 1 + P, D], fully written: dfull[i, 1 + p, :] = sum over the samples s with idx[s] == i, in ascending s, of
+ *        dout[s, 1 + p, :] + atts[s, p] / wsum[s] * dout[s, 0, :] (fp32 sums, one rounding); dfull[i, 0, :] = 0; an image that no sample
+ *        reads gets zeros.  No atomics: bit-reproducible with and without XFM_DETERMINISTIC. */
+int xfm_region_pool_fwd(const xfm_bf16* full, const int* idx, const uint8_t* atts, int n_img, int bs, int P, int D, xfm_bf16* out,
+                        float* wsum, void* stream);
+int xfm_region_pool_bwd(const xfm_bf16* dout, const int* idx, const uint8_t* atts, const float* wsum, int n_img, int bs, int P, int D,
+                        xfm_bf16* dfull, void* stream);
+/* Box loss (XFMBase.get_bbox_loss, xfm.py:815-840): coord / target fp32 [bs, 4] as (cx, cy, w, h), 16-byte aligned; is_image fp32 [bs] or
+ * NULL (row weight w_r = 1 - is_image[r], else 1).  out[0] = sum_r w_r sum_j |coord - target| / num, out[1] = sum_r w_r (1 - GIoU of the
+ * paired xyxy boxes) / num, num = sum_r w_r.  If any box of either set has x2 < x1 or y2 < y1, out[1] = 0 and carries no gradient (the
+ * reference's whole-batch rule).  One workgroup, fixed-order sums, fp64 inside, rounded to fp32 once.
+ * state fp64 [bs, 8] (written by fwd): d out[0] / d coord[r, :], d out[1] / d coord[r, :].
+ *   bwd: dcoord fp32 [bs, 4] = g[0] * state[r, 0:4] + g[1] * state[r, 4:8]; g fp32 [2] on the device (the two upstream scalars). */
+int xfm_box_loss_fwd(const float* coord, const float* target, const float* is_image, int bs, float* out, double* state, void* stream);
+int xfm_box_loss_bwd(const double* state, const float* g, int bs, float* dcoord, void* stream);
 
 /* ---- Flat-arena optimiser step (optim.py:4-50 + clip, apex_ddp_accelerator.py:100-110) --------------------------- */
 typedef struct {

@@ -7,6 +7,7 @@ blocks run as ONE autograd node whose forward/backward are explicit sequences of
 (xfm_amd.functional); PyTorch autograd only sees the patch/cls assembly before it and the pooling after it.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -336,11 +337,35 @@ class _TrunkFn(torch.autograd.Function):
         return dstream.view(B, N, D), None, None
 
 
+class _RegionPoolFn(torch.autograd.Function):
+    """xfm_region_pool_fwd / bwd: the gather and the pooled row in one pass; the backward sums the samples of an image in ascending
+    order without atomics (ATen's index_select backward is an atomic index_add: not reproducible once two samples share an image)."""
+
+    @staticmethod
+    def forward(ctx, full, idx32, atts_u8):
+        out, wsum = Fx.region_pool_fwd(full, idx32, atts_u8)
+        ctx.save_for_backward(idx32, atts_u8, wsum)
+        ctx.n_img = full.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        idx32, atts_u8, wsum = ctx.saved_tensors
+        return Fx.region_pool_bwd(dout.contiguous(), idx32, atts_u8, wsum, ctx.n_img), None, None
+
+
+REGION_GLUE_FUSED = os.environ.get("XFM_REGION_GLUE", "1") != "0"   # A/B knob (tools/bench_region_step.py): 0 = the ATen glue on the device too
+
+
 def region_outputs(full, idx_to_group_img, image_atts):
     """The region call form's per-sample output (beit2.py:467-475): sample i reads the normalised patch rows of image
     idx_to_group_img[i] and pools its own pseudo-cls as their image_atts-weighted mean (fp32 sums, one rounding to the tower's
-    bf16).  A row gather and a [bs, P] x [bs, P, D] contraction on a handful of samples: device-side glue (differentiable ATen ops on
-    the HIP tensors), no tower kernel involved."""
+    bf16).  HIP tensors: one kernel each way (_RegionPoolFn).  CPU tensors: the same arithmetic as differentiable ATen ops."""
+    if full.is_cuda and full.dtype == torch.bfloat16 and REGION_GLUE_FUSED:
+        atts = image_atts.to(device=full.device)[:, 1:]
+        assert atts.shape == (idx_to_group_img.numel(), full.shape[1] - 1), "image_atts is [bs, 1 + patches]"
+        return _RegionPoolFn.apply(full.contiguous(), idx_to_group_img.to(device=full.device, dtype=torch.int32).view(-1).contiguous(),
+                                   atts.to(torch.uint8).contiguous())
     idx = idx_to_group_img.to(device=full.device, dtype=torch.long).view(-1)
     x_bs = full[:, 1:, :].index_select(0, idx)
     w = image_atts.to(device=full.device)[:, 1:].to(torch.float32)

@@ -37,6 +37,7 @@ int xfm_cu_count() {
 #include "encoder.hip"
 #include "losses.hip"
 #include "losses_soft.hip"
+#include "region.hip"
 #include "dp.hip"
 
 #define ST(s) ((hipStream_t)(s))
@@ -302,6 +303,25 @@ int xfm_mixup(float* x, int B, int C, int H, int W, const float* lam, const int*
 int xfm_mixup_target(const int64_t* labels, const float* lam, int B, int num_classes, float smoothing, float* out, long ldo, void* stream) {
   XFM_REQUIRE(labels && lam && out, "mixup_target: null operand");
   return xfm_mixup_target_impl(labels, lam, B, num_classes, smoothing, out, ldo, ST(stream));
+}
+
+int xfm_region_pool_fwd(const xfm_bf16* full, const int* idx, const uint8_t* atts, int n_img, int bs, int P, int D, xfm_bf16* out,
+                        float* wsum, void* stream) {
+  XFM_REQUIRE(full && idx && atts && out && wsum, "region_pool_fwd: null operand");
+  return xfm_region_pool_fwd_impl(full, idx, atts, n_img, bs, P, D, out, wsum, ST(stream));
+}
+int xfm_region_pool_bwd(const xfm_bf16* dout, const int* idx, const uint8_t* atts, const float* wsum, int n_img, int bs, int P, int D,
+                        xfm_bf16* dfull, void* stream) {
+  XFM_REQUIRE(dout && idx && atts && wsum && dfull, "region_pool_bwd: null operand");
+  return xfm_region_pool_bwd_impl(dout, idx, atts, wsum, n_img, bs, P, D, dfull, ST(stream));
+}
+int xfm_box_loss_fwd(const float* coord, const float* target, const float* is_image, int bs, float* out, double* state, void* stream) {
+  XFM_REQUIRE(coord && target && out && state, "box_loss_fwd: null operand");
+  return xfm_box_loss_fwd_impl(coord, target, is_image, bs, out, state, ST(stream));
+}
+int xfm_box_loss_bwd(const double* state, const float* g, int bs, float* dcoord, void* stream) {
+  XFM_REQUIRE(state && g && dcoord, "box_loss_bwd: null operand");
+  return xfm_box_loss_bwd_impl(state, g, bs, dcoord, ST(stream));
 }
 
 int xfm_adamw(const xfm_adamw_args* a, void* stream) {

@@ -550,6 +550,57 @@ def pool_rows_bwd(dy, B, N):
     return out
 
 
+def region_pool_fwd(full, idx, atts):
+    """full bf16 [n_img, 1 + P, D], idx int32 [bs], atts uint8 [bs, P] -> (out bf16 [bs, 1 + P, D], wsum fp32 [bs]): sample s gets the patch
+    rows of image idx[s] bit for bit and, as row 0, their atts-weighted mean (fp32 sums, one rounding)."""
+    _dev(full)
+    n_img, N, D = full.shape
+    bs = idx.numel()
+    assert full.dtype == BF16 and full.is_contiguous()
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.is_cuda
+    assert atts.dtype == torch.uint8 and atts.is_contiguous() and atts.shape == (bs, N - 1) and atts.is_cuda
+    out = torch.empty((bs, N, D), dtype=BF16, device=full.device)
+    wsum = torch.empty(bs, dtype=F32, device=full.device)
+    check(_lib.load().xfm_region_pool_fwd(full.data_ptr(), idx.data_ptr(), atts.data_ptr(), n_img, bs, N - 1, D, out.data_ptr(),
+                                          wsum.data_ptr(), _stream()), "region_pool_fwd")
+    return out, wsum
+
+
+def region_pool_bwd(dout, idx, atts, wsum, n_img):
+    """Gradient of region_pool_fwd w.r.t. `full`: bf16 [n_img, 1 + P, D], the samples of an image summed in ascending order (no atomics)."""
+    _dev(dout)
+    bs, N, D = dout.shape
+    assert dout.dtype == BF16 and dout.is_contiguous() and idx.numel() == bs and atts.shape == (bs, N - 1) and wsum.numel() == bs
+    dfull = torch.empty((n_img, N, D), dtype=BF16, device=dout.device)
+    check(_lib.load().xfm_region_pool_bwd(dout.data_ptr(), idx.data_ptr(), atts.data_ptr(), wsum.data_ptr(), n_img, bs, N - 1, D,
+                                          dfull.data_ptr(), _stream()), "region_pool_bwd")
+    return dfull
+
+
+def box_loss_fwd(coord, target, is_image=None):
+    """coord / target fp32 [bs, 4] (cx, cy, w, h), is_image fp32 [bs] or None -> (out fp32 [2] = (loss_bbox, loss_giou), state fp64
+    [bs, 8] for box_loss_bwd).  See xfm_box_loss_fwd."""
+    _dev(coord)
+    bs = coord.shape[0]
+    for t in (coord, target):
+        assert t.dtype == F32 and t.is_contiguous() and t.shape == (bs, 4) and t.is_cuda
+    assert is_image is None or (is_image.dtype == F32 and is_image.is_contiguous() and is_image.numel() == bs and is_image.is_cuda)
+    out = torch.empty(2, dtype=F32, device=coord.device)
+    state = torch.empty((bs, 8), dtype=torch.float64, device=coord.device)
+    check(_lib.load().xfm_box_loss_fwd(coord.data_ptr(), target.data_ptr(), _ptr(is_image), bs, out.data_ptr(), state.data_ptr(), _stream()),
+          "box_loss_fwd")
+    return out, state
+
+
+def box_loss_bwd(state, g):
+    """state from box_loss_fwd, g fp32 [2] (device): the gradients of the two losses -> dcoord fp32 [bs, 4]."""
+    bs = state.shape[0]
+    assert state.dtype == torch.float64 and state.is_contiguous() and g.dtype == F32 and g.numel() == 2 and g.is_contiguous() and g.is_cuda
+    dcoord = torch.empty((bs, 4), dtype=F32, device=state.device)
+    check(_lib.load().xfm_box_loss_bwd(state.data_ptr(), g.data_ptr(), bs, dcoord.data_ptr(), _stream()), "box_loss_bwd")
+    return dcoord
+
+
 def mim_loss_fwd(x, t, mask):
     """-> sums fp32 [3] = (sum (x-t)^2 over masked patch rows, over cls rows, number of masked patches); x, t bf16 [B, N, D]."""
     _dev(x)

@@ -106,8 +106,16 @@ class XFM(XFMBase):
         """`text_lens` (extension; host-side lengths of the prefix masks `text_atts`, e.g. `text_atts.sum(1)` taken BEFORE the batch
         was uploaded): run the text and fusion towers on unpadded token rows (xfm_amd.packing).  Same values on every token that
         any loss reads; None = the reference's padded computation."""
-        if ret_bbox_loss or ret_bbox_giou:
-            raise NotImplementedError("bbox / region losses (model_pretrain.py:39-41,81-85) are outside the hot-path scope")
+        if ret_bbox_giou and not ret_bbox_loss:
+            raise ValueError("ret_bbox_giou needs ret_bbox_loss: the box head reads image_embeds_fullatts, which only the region call of "
+                             "get_vision_embeds returns (model_pretrain.py:39-41, 81-82; a NameError in the reference)")
+        if ret_bbox_loss:
+            if image_atts is None or idx_to_group_img is None:
+                raise ValueError("ret_bbox_loss takes the region batch's image_atts and idx_to_group_img (model_pretrain.py:39-41)")
+            if text_lens is not None:
+                raise NotImplementedError("text_lens with ret_bbox_loss: the packed 4B fusion pass (image-major layout, K/V prefetch) is "
+                                          "not built for per-sample region image_atts; call the region step without text_lens")
+            ret_mim_loss = False   # model_pretrain.py:68: `ret_mim_loss and not ret_bbox_loss`
         if self.learnable_temp:
             self.temp.data.clamp_(self.min_temp, self.max_temp)  # via .data: leaves the arena's weight version untouched
         w = self.weights_map.get(data_source, None)
@@ -165,6 +173,12 @@ class XFM(XFMBase):
                 image_embeds, image_embeds_masked = both[:B], both[B:]
             from .xfm import _ones_mask
             image_atts = _ones_mask(image_embeds)
+        elif ret_bbox_loss:
+            # region batch: bs samples over fewer images.  image_embeds [bs, N, D] = every sample's patch rows + its own pooled row,
+            # image_atts [bs, N] its ragged region mask (a key mask of every cross-attention below: never tagged all-ones),
+            # image_full [n_img, N, D] the tower's whole-image output, which the box head reads
+            image_embeds, image_atts, image_full = self.get_vision_embeds(image, image_atts=image_atts.to(image.device),
+                                                                          idx_to_group_img=idx_to_group_img, gather_fullatts=False)
         else:
             image_embeds, image_atts = self.get_vision_embeds(image)
         _marks.mark("vit fwd end")
@@ -221,8 +235,21 @@ class XFM(XFMBase):
                     loss_mim = self.get_mim_loss(image_embeds_masked, image_embeds, ids_mask)
             if w is not None:
                 loss_mim = loss_mim * w
+        loss_bbox = loss_giou = zero
+        if ret_bbox_giou:   # model_pretrain.py:81-85
+            from . import beit2 as _beit2
+            from .functional import attn_grouped_ok
+            from .xfm import gather_images
+            idx = idx_to_group_img.to(image.device).view(-1)
+            if image.is_cuda and attn_grouped_ok(text_ids.shape[1], image_full.shape[1]):
+                # the bs rows attend n_img whole images: hand the fusion tower the images once and the row -> image index
+                output_coord = self.predict_bbox(image_full, text_ids, text_atts, text_embeds, image_index=idx)
+            else:
+                output_coord = self.predict_bbox(gather_images(image_full, idx), text_ids, text_atts, text_embeds)
+            loss_bbox, loss_giou = self.get_bbox_loss(output_coord, target_bbox.to(image.device), is_image=is_image,
+                                                      fused=image.is_cuda and _beit2.REGION_GLUE_FUSED)
         return {'loss_itc': loss_itc, 'loss_itm': loss_itm, 'loss_mlm': loss_mlm, 'loss_mim': loss_mim,
-                'loss_bbox': zero, 'loss_giou': zero}
+                'loss_bbox': loss_bbox, 'loss_giou': loss_giou}
 
     def forward_text(self, text_ids=None, text_atts=None, text_ids_masked=None, masked_pos=None, masked_ids=None):
         return {'loss_mlm': self.get_mlm_loss(text_ids_masked, text_atts, None, None, masked_pos, masked_ids)}

@@ -3,10 +3,10 @@
 Mirrors (names, argument meaning, ordering):
   * create_optimizer    optim.py:4-50      4 AdamW groups (decay / no-decay) x (lr / lr * lr_mult for model.init_params), betas (0.9, 0.98)
   * create_scheduler    scheduler.py:4-30  linear warm-up then linear decay (LambdaLR)
-  * run_image_iter / run_text_iter / train   Pretrain.py:61-91, 124-139, 141-303
+  * run_image_iter / run_region_iter / run_text_iter / train   Pretrain.py:61-91, 94-121, 124-139, 141-303
 What differs, on purpose: the reference reads every loss with `.item()` right after each backward (a device sync per source per
 step, Pretrain.py:79-91); here the loss tensors are queued and only read when a log line is due (`LossMeters.flush`), so the host
-keeps enqueueing the next step while the GPU runs.  Region batches (run_region_iter) are outside the hot-path scope."""
+keeps enqueueing the next step while the GPU runs."""
 import math
 from collections import OrderedDict
 
@@ -141,6 +141,24 @@ def run_image_iter(model, image_batch, optimizer, accelerator, metric_logger, de
             metric_logger.update(**{name: loss[key]})
 
 
+def run_region_iter(model, region_batch, optimizer, accelerator, metric_logger, device, config, data_source='region', ret_mim_loss=True,
+                    ret_match_loss=True, ret_mlm_loss=True, ret_itc_loss=True):
+    """Pretrain.py:94-121: one region batch (bs samples over fewer images) through the model with the box losses, backward, and NO
+    optimizer step -- the gradients accumulate into the image iteration that follows.  `config` is the global the reference reads."""
+    image = _to(device, region_batch[0])
+    idx_to_group_img, text_ids, text_atts, text_ids_masked, masked_pos, masked_ids, image_atts, target_bbox, is_image = \
+        (_to(device, t) for t in region_batch[1:])
+    if config['calc_image_bbox_loss']:
+        is_image = None
+    loss = model(image, text_ids, text_atts, text_ids_masked=text_ids_masked, masked_pos=masked_pos, masked_ids=masked_ids,
+                 image_atts=image_atts, idx_to_group_img=idx_to_group_img, target_bbox=target_bbox, is_image=is_image,
+                 ret_mim_loss=ret_mim_loss, ret_bbox_loss=config['ret_bbox_loss'], ret_match_loss=ret_match_loss,
+                 ret_mlm_loss=ret_mlm_loss, ret_bbox_giou=config['ret_bbox_giou'], ret_itc_loss=ret_itc_loss, data_source=data_source)
+    _backward(accelerator, loss['loss_itc'] + loss['loss_itm'] + loss['loss_mlm'] + loss['loss_bbox'] + loss['loss_giou'], optimizer, False)
+    metric_logger.update(loss_ritc=loss['loss_itc'], loss_ritm=loss['loss_itm'], loss_rmlm=loss['loss_mlm'],
+                         loss_rbbox=loss['loss_bbox'], loss_rgiou=loss['loss_giou'])
+
+
 def run_text_iter(model, batch, optimizer, accelerator, metric_logger, device):
     """Pretrain.py:124-139: a text-only MLM step with its own optimizer step."""
     text_ids, text_atts, text_ids_masked, masked_pos, masked_ids = (_to(device, t) for t in batch)
@@ -159,8 +177,6 @@ def train(model, image_loader, data_loaders, optimizer, epoch_info, device, sche
     called on the reference's schedule (ckpt_frequent epochs / ckpt_frequent_step steps) when given."""
     model.train()
     image_loader_aux, image_loader_web, image_loader_imagenet, region_loader, text_loader = data_loaders
-    if region_loader is not None:
-        raise NotImplementedError("region batches (run_region_iter, Pretrain.py:94-121) are outside the hot-path scope")
     start_epoch, max_epoch = epoch_info
     metric_logger = LossMeters()
     step_per_epoch = math.ceil(config['train_dataset_size'] / (config['batch_size'] * world_size))
@@ -171,7 +187,7 @@ def train(model, image_loader, data_loaders, optimizer, epoch_info, device, sche
     stop_mim, stop_mm = config.get('stop_calc_mim', inf), config.get('stop_calc_mm', inf)
     iters = {name: (iter(ld) if ld is not None else None)
              for name, ld in (('web', image_loader_web), ('imagenet', image_loader_imagenet), ('text', text_loader),
-                              ('aux', image_loader_aux))}
+                              ('aux', image_loader_aux), ('region', region_loader))}
     # utils.MetricLogger.log_every stops after (end_epoch - start_epoch) * step_per_epoch batches (Pretrain.py:205-209): a run resumed at
     # epoch k trains the REMAINING epochs, whatever the loader's length
     total_steps = (max_epoch - start_epoch) * step_per_epoch if max_epoch is not None else None
@@ -182,6 +198,9 @@ def train(model, image_loader, data_loaders, optimizer, epoch_info, device, sche
                      ret_itc_loss=global_step < stop_itc)
         if iters['text'] is not None:
             run_text_iter(model, next(iters['text']), optimizer, accelerator, metric_logger, device)
+        if iters['region'] is not None:
+            run_region_iter(model, next(iters['region']), optimizer, accelerator, metric_logger, device, config, data_source='region',
+                            **gates)
         if iters['web'] is not None:  # (the reference computes a do_optm here and does not pass it, Pretrain.py:225-227)
             run_image_iter(model, next(iters['web']), optimizer, accelerator, metric_logger, device, data_source='web', **gates)
         if iters['aux'] is not None:

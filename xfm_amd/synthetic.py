@@ -216,3 +216,47 @@ def region_case(n_images, grid=14):
         m[y0:y0 + h, x0:x0 + w] = 1
         atts[i, 1:] = m.reshape(-1)
     return idx, atts
+
+
+def region_batch(batch_size, max_images, max_regions, seed=1234, image_res=224, patch_size=16, max_tokens=30, max_masks=15, vocab=VOCAB):
+    """A region batch in the tuple layout that run_region_iter unpacks (Pretrain.py:94-99; the collate of the reference's region dataset):
+    (image [n_img, 3, R, R], idx_to_group_img [bs], text_ids, text_atts, text_ids_masked, masked_pos, masked_ids [bs, ...],
+    image_atts [bs, 1 + grid^2] of 0 / 1, target_bbox fp32 [bs, 4] as (cx, cy, w, h) in [0, 1], is_image [bs] of 0 / 1).
+    bs = batch_size samples, image by image: every image carries 1..max_regions of them, at most max_images images.  A sample is either
+    the whole image (is_image = 1: all patches, box (0.5, 0.5, 1, 1)) or a rectangle of patches with the box that bounds it -- every mask
+    has at least one patch."""
+    assert max_images * max_regions >= batch_size, "max_images * max_regions samples at the most"
+    grid = image_res // patch_size
+    tag = f"region{seed}"
+    counts, left = [], batch_size
+    draw = uniform01(tag + ".count", max_images)
+    for i in range(max_images):
+        if left == 0:
+            break
+        images_after = max_images - i - 1
+        lo = max(1, left - images_after * max_regions)   # what this image must take for the rest to fit
+        k = min(max(lo, 1 + int(draw[i] * max_regions)), max_regions, left)
+        counts.append(k)
+        left -= k
+    n_img = len(counts)
+    idx = np.repeat(np.arange(n_img), counts)
+    u = uniform01(tag + ".box", batch_size * 5).reshape(batch_size, 5)
+    atts = np.zeros((batch_size, 1 + grid * grid), dtype=np.int64)
+    atts[:, 0] = 1
+    target = np.zeros((batch_size, 4), dtype=np.float32)
+    is_image = np.zeros(batch_size, dtype=np.int64)
+    for s in range(batch_size):
+        if s > 0 and u[s, 4] < 0.2:   # the whole image with its caption (never sample 0: the box losses divide by the number of regions)
+            is_image[s] = 1
+            y0, x0, h, w = 0, 0, grid, grid
+        else:
+            h, w = 1 + int(u[s, 0] * (grid - 1)), 1 + int(u[s, 1] * (grid - 1))
+            y0, x0 = int(u[s, 2] * (grid - h + 1)), int(u[s, 3] * (grid - w + 1))
+        m = np.zeros((grid, grid), dtype=np.int64)
+        m[y0:y0 + h, x0:x0 + w] = 1
+        atts[s, 1:] = m.reshape(-1)
+        target[s] = [(x0 + 0.5 * w) / grid, (y0 + 0.5 * h) / grid, w / grid, h / grid]
+    b = pretrain_batch(batch_size, seed=seed, image_res=image_res, max_tokens=max_tokens, max_masks=max_masks, vocab=vocab, with_image=False)
+    image = gaussian(tag + ".image", (n_img, 3, image_res, image_res), 1.0)
+    return (image, torch.from_numpy(idx), b["text_ids"], b["text_atts"], b["text_ids_masked"], b["masked_pos"], b["masked_ids"],
+            torch.from_numpy(atts), torch.from_numpy(target), torch.from_numpy(is_image))

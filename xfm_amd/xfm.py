@@ -23,6 +23,7 @@ import torch.nn.functional as F
 from . import functional as Fx
 from . import marks as _marks
 from .arena import LinearSlot, ParamArena
+from . import beit2 as _beit2
 from .beit2 import _Affine, beit_base_patch16
 from .ops import itc_loss, layer_norm, linear_slot, row_normalize, small_ce
 from .xroberta import RobertaConfig, RobertaForMaskedLM, _Lin, rowwise
@@ -231,6 +232,46 @@ class _MimLossFn(torch.autograd.Function):
         return dx, None, None, None
 
 
+class _GatherImagesFn(torch.autograd.Function):
+    """full [n_img, N, D] -> full.index_select(0, idx) (xfm.py:577-597: one copy of the whole-image output per sample).  The backward
+    folds the sample gradients onto their images in ascending sample order with xfm_rows_index_sum (fp32 sums, one rounding) -- ATen's
+    index_select backward is an atomic index_add, not reproducible once two samples share an image."""
+
+    @staticmethod
+    def forward(ctx, full, idx):
+        ctx.save_for_backward(idx.to(torch.int32).contiguous())
+        ctx.n_img = full.shape[0]
+        return full.index_select(0, idx)
+
+    @staticmethod
+    def backward(ctx, dout):
+        idx32, = ctx.saved_tensors
+        bs, N, D = dout.shape
+        return Fx.rows_index_sum(dout.contiguous().view(bs * N, D), idx32, ctx.n_img, N).view(ctx.n_img, N, D), None
+
+
+def gather_images(full, idx):
+    if full.is_cuda and full.dtype == BF16 and full.shape[-1] % 8 == 0:
+        return _GatherImagesFn.apply(full.contiguous(), idx)
+    return full.index_select(0, idx)
+
+
+class _BoxLossFn(torch.autograd.Function):
+    """(loss_bbox, loss_giou) of get_bbox_loss as one kernel each way (xfm_box_loss_fwd / bwd); the target carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, coord, target, is_image):
+        out, state = Fx.box_loss_fwd(coord, target, is_image)
+        ctx.save_for_backward(state)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_bbox, g_giou):
+        state, = ctx.saved_tensors
+        g = torch.stack([g_bbox.reshape(()), g_giou.reshape(())]).to(torch.float32)
+        return Fx.box_loss_bwd(state, g), None, None
+
+
 class XFMBase(nn.Module):
     def __init__(self, config=None, load_vision_params=False, load_text_params=False, use_contrastive_loss=False,
                  use_matching_loss=False, use_mlm_loss=False, use_bbox_loss=False, config_text=None):
@@ -333,16 +374,23 @@ class XFMBase(nn.Module):
             super().zero_grad(set_to_none=set_to_none)
 
     # ---- towers ---------------------------------------------------------------------------------
-    def get_vision_embeds(self, image, image_atts=None, idx_to_group_img=None, do_mask=False, ids_mask=None, split_stream=None):
+    def get_vision_embeds(self, image, image_atts=None, idx_to_group_img=None, do_mask=False, ids_mask=None, split_stream=None,
+                          gather_fullatts=True):
+        """`gather_fullatts=False` (extension, region call form only): the third result is the tower's [n_img, N, D] output itself, not
+        its per-sample copy -- for a caller that hands the fusion tower the images once with a row -> image index (predict_bbox)."""
         self._ready()
         if idx_to_group_img is not None:   # fewer images than samples (xfm.py:574-597)
             idx = idx_to_group_img.to(image.device).view(-1)
             if image_atts is None:     # every sample sees its whole image: the tower's output, one copy per sample
-                image_embeds_fullatts = self.vision_encoder(image).index_select(0, idx)
+                image_embeds_fullatts = gather_images(self.vision_encoder(image), idx)
                 return image_embeds_fullatts, _ones_mask(image_embeds_fullatts)
             assert image_atts.size(0) == idx.size(0)
             image_embeds, image_embeds_fullatts = self.vision_encoder(image, idx_to_group_img=idx, image_atts=image_atts)
-            return image_embeds, image_atts, image_embeds_fullatts.index_select(0, idx)
+            if not gather_fullatts:
+                return image_embeds, image_atts, image_embeds_fullatts
+            if not _beit2.REGION_GLUE_FUSED:   # A/B knob XFM_REGION_GLUE=0: ATen's gather and its index_add backward
+                return image_embeds, image_atts, image_embeds_fullatts.index_select(0, idx)
+            return image_embeds, image_atts, gather_images(image_embeds_fullatts, idx)
         if do_mask:
             image_embeds, id_masked = self.vision_encoder(image, do_mask=True, ids_mask=ids_mask, split_stream=split_stream)
             if isinstance(image_embeds, tuple):   # two views as two passes (the second one on `split_stream`)
@@ -401,20 +449,26 @@ class XFMBase(nn.Module):
                    encoder_attention_mask=image_atts, return_dict=True, **kw).last_hidden_state
 
     # ---- grounding head ----------------------------------------------------------------------------
-    def predict_bbox(self, image_embeds, text_ids, text_atts, text_embeds, is_pretrain=True):
-        """xfm.py:843-854: fused [CLS] -> bbox_head -> sigmoid, (cx, cy, w, h) in [0, 1]."""
-        assert image_embeds.size(0) == text_ids.size(0) == text_atts.size(0)
+    def predict_bbox(self, image_embeds, text_ids, text_atts, text_embeds, is_pretrain=True, image_index=None):
+        """xfm.py:843-854: fused [CLS] -> bbox_head -> sigmoid, (cx, cy, w, h) in [0, 1].
+        `image_index` (extension, see get_cross_embeds): `image_embeds` holds every image once and sample r reads image image_index[r]."""
+        assert (image_embeds.size(0) if image_index is None else image_index.numel()) == text_ids.size(0) == text_atts.size(0)
         image_atts = torch.ones(image_embeds.shape[:2], dtype=torch.long, device=image_embeds.device)
         output_cls = self.get_cross_embeds(image_embeds, image_atts, text_ids=text_ids, text_atts=text_atts, text_embeds=text_embeds,
-                                           is_pretrain=is_pretrain)[:, 0, :]
+                                           is_pretrain=is_pretrain, image_index=image_index)[:, 0, :]
         return self.bbox_head(output_cls).float().sigmoid()
 
-    def get_bbox_loss(self, output_coord, target_bbox, is_image=None):
+    def get_bbox_loss(self, output_coord, target_bbox, is_image=None, fused=False):
         """L1 + GIoU (xfm.py:815-840).  The reference checks for degenerate boxes with `.any()` on the host and then zeroes the GIoU
         term of the whole batch; the same rule here is a device-side select (no sync), evaluated on stand-in boxes when it fires so
-        that no NaN reaches the backward."""
+        that no NaN reaches the backward.
+        `fused=True` (the region pre-training step): both losses and their gradient as one kernel each way (xfm_box_loss_fwd / bwd)
+        instead of ~30 ATen launches each way; HIP tensors only."""
         from . import box_ops
         output_coord, target_bbox = output_coord.float(), target_bbox.float()
+        if fused:
+            w = None if is_image is None else is_image.to(device=output_coord.device, dtype=torch.float32).reshape(-1).contiguous()
+            return _BoxLossFn.apply(output_coord.contiguous(), target_bbox.detach().contiguous(), w)
         loss_bbox = F.l1_loss(output_coord, target_bbox, reduction='none')
         boxes1 = box_ops.box_cxcywh_to_xyxy(output_coord)
         boxes2 = box_ops.box_cxcywh_to_xyxy(target_bbox)
