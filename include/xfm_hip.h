@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 11
+#define XFM_ABI_VERSION 12
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -65,10 +65,21 @@ int xfm_gemm_nt_ksplit(const xfm_bf16* A, long lda, const xfm_bf16* B, long ldb,
  * The split partials are written to `workspace` (xfm_gemm_tn_workspace bytes for splits_hint 0; may be 0) and summed
  * in a fixed order by a reduce kernel; a single split updates dW in place; only splits without a workspace fall back to
  * fp32 atomics.  Large edge-free shapes (M % 64 == 0; N, K % 256 == 0) run on a 256x256 pipelined kernel.
- * splits_hint: 0 = auto, > 0 = that many splits of the 128x128 kernel. */
+ * splits_hint: 0 = auto, > 0 = that many splits of the 128x128 kernel; the kernel A/B switches -3 = the 256x256 kernel wherever the
+ * shape allows it, -4 = never the 256x256 kernel, -5 = the register-staged 128x128 kernel instead of the ring kernel.
+ * A workspace smaller than the route needs is not an error: the 256x256 route steps down to the 128x128 plan, and that one to atomics.
+ * xfm_gemm_tn_workspace and xfm_gemm_tn read ONE plan (xfm_gemm_tn_plan): the query is the plan of (M, N, K, ldy = N, ldx = K,
+ * splits_hint 0) with no limit on the workspace. */
 long xfm_gemm_tn_workspace(int M, int N, int K);
 int xfm_gemm_tn(const xfm_bf16* dY, long ldy, const xfm_bf16* X, long ldx, float* dW, long ldw, float* dbias, int M, int N,
                 int K, int splits_hint, float* workspace, long workspace_bytes, void* stream);
+/* The plan xfm_gemm_tn follows for these arguments and a workspace of workspace_bytes (LONG_MAX: whatever it wants; 0: none) -- for
+ * sizing the workspace of a call with a splits_hint, and for attributing a call to its kernels as with xfm_gemm_nt_plan (ABI 12).
+ * *kernel: 0 = 256x256 pipeline, 1 = 128x128 ring, 2 = 128x128 register-staged; *splits = M-splits; *workspace_used = the bytes the
+ * route writes through (0: one split in place, or atomics).  For a ragged M that runs as 256x256 body + last M % 64 rows the plan is
+ * the body's; the rest is one more single-split 128x128 launch and needs no workspace. */
+int xfm_gemm_tn_plan(int M, int N, int K, long ldy, long ldx, int splits_hint, long workspace_bytes, int* kernel, int* splits,
+                     long* workspace_used);
 /* nb (1..4) weight gradients of ONE shape (same M, N, K and leading dimensions; host arrays of device pointers; dbias / its entries may be
  * NULL) as one launch + one reduce -- the three 768 x 768 projections of a RobertaLayer with cross-attention (xroberta.py:201-304).  Falls
  * back to nb xfm_gemm_tn calls when N or K is not a multiple of 128 or the workspace is smaller than xfm_gemm_tn_batch_workspace(). */

@@ -282,14 +282,142 @@ def test_attention_backward_workspace_table():
         [(kw, env, got[i], w) for i, (kw, env, w) in enumerate(ATTN_WORKSPACE_TABLE) if got[i] != w]
 
 
-def test_attention_sources_set_the_lds_attribute_once_and_include_at_the_top():
-    """One launcher owns hipFuncAttributeMaxDynamicSharedMemorySize for every attention kernel instantiation, and attention.hip (the host
-    side) pulls in its kernel families before its first function: no file order to work around."""
+GEMM_SOURCES = ("gemm.hip", "gemm_common.h", "gemm_nt_small.hip", "gemm_nt_256.hip", "gemm_tn_small.hip", "gemm_tn_256.hip", "gemm_cast.hip")
+
+
+def test_kernel_sources_set_the_lds_attribute_once_and_include_at_the_top():
+    """One launcher (lds_launch, common.h) owns hipFuncAttributeMaxDynamicSharedMemorySize for every kernel instantiation of the library,
+    no hand-kept `attr_set` guard is left, and attention.hip / gemm.hip (the host sides) pull in their kernel families before their first
+    function: no file order to work around."""
     csrc = os.path.join(ROOT, "xfm_amd", "csrc")
     assert sorted(f for f in os.listdir(csrc) if f.startswith("attention")) == sorted(ATTENTION_SOURCES)
-    text = {f: open(os.path.join(csrc, f)).read() for f in ATTENTION_SOURCES}
+    assert sorted(f for f in os.listdir(csrc) if f.startswith("gemm")) == sorted(GEMM_SOURCES)
+    text = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".h"))}
     assert sum(s.count("hipFuncSetAttribute") for s in text.values()) == 1
-    lines = text["attention.hip"].splitlines()
-    first_fn = next(i for i, l in enumerate(lines) if re.match(r"^(static |int |long |template |__global__ |struct |enum )", l))
-    includes = [i for i, l in enumerate(lines) if l.lstrip().startswith("#include")]
-    assert includes and max(includes) < first_fn, (includes, first_fn)
+    assert not [f for f, s in text.items() if "attr_set" in s]
+    for host in ("attention.hip", "gemm.hip"):
+        lines = text[host].splitlines()
+        first_fn = next(i for i, l in enumerate(lines) if re.match(r"^(static |int |long |template |__global__ |struct |enum )", l))
+        includes = [i for i, l in enumerate(lines) if l.lstrip().startswith("#include")]
+        assert includes and max(includes) < first_fn, (host, includes, first_fn)
+        assert {l.split('"')[1] for l in lines if l.startswith('#include "')} >= {f for f in text if f.startswith(host[:-4] + "_")}, host
+
+
+# (query, arguments, bytes): the answers of the library BEFORE one plan served the query and the launch (the ladder of xfm_gemm_tn written
+# twice, the batched hint twice, the K-slice rule twice), recorded from it.  Host-only calls; without a device the CU count reads 256.
+GEMM_WORKSPACE_TABLE = [
+    ("tn", (4096, 768, 1536), 37748736),            # 256 x 256 kernel: 18 tiles x 8 splits
+    ("tn", (4032, 768, 1536), 28311552),            # under 4096 rows: 128 x 128 plan, 72 tiles x 6 splits
+    ("tn", (4160, 768, 1536), 37748736),
+    ("tn", (4096, 768, 1280), 27525120),            # 15 tiles of 256 x 256 < 18: 128 x 128 plan
+    ("tn", (4096, 1536, 1536), 66060288),
+    ("tn", (21624, 2304, 768), 63700992),           # ragged M: the 21568-row body's planes
+    ("tn", (8250, 768, 1536), 61341696),            # ragged, body 8192 rows
+    ("tn", (8190, 768, 1536), 28311552),            # ragged, body 8128 rows < 8192: one 128 x 128 call
+    ("tn", (8250, 768, 1280), 27525120),            # ragged, 15 tiles
+    ("tn", (21624, 2432, 768), 29884416),           # ragged, N % 256 != 0
+    ("tn", (1920, 768, 768), 0),                    # 4 splits x 36 tiles = 9.4 MB < 16 MB: atomics
+    ("tn", (3360, 768, 768), 0),                    # 7 x 36 x 64 KB = 16.5e6 bytes < 16 MiB
+    ("tn", (3840, 768, 768), 18874368),             # 8 x 36 x 64 KB
+    ("tn", (928, 768, 768), 0),                     # the two-split case, 4.7 MB
+    ("tn", (928, 3072, 768), 18874368),             # ... with 144 tiles
+    ("tn", (600, 3072, 768), 0),                    # one split
+    ("tn", (4096, 1000, 768), 25165824),            # N % 128 != 0: 8 x 6 tiles
+    ("tn", (5252, 3072, 768), 28311552),            # ragged under 8192 rows (the fusion tower)
+    ("tn", (0, 768, 768), 0),
+    ("batch", (1, 1920, 768, 768), 0),
+    ("batch", (2, 1920, 768, 768), 28311552),
+    ("batch", (4, 1920, 768, 768), 28311552),
+    ("batch", (5, 1920, 768, 768), 0),              # more than TN_BATCH_MAX: single calls
+    ("batch", (3, 5248, 768, 768), 28311552),
+    ("batch", (2, 1920, 1000, 768), 0),             # N % 128 != 0: single calls
+    ("batch", (2, 300, 768, 768), 23592960),
+    ("group", (12608, [(768, 768)] * 4), 134742016),
+    ("group", (12608, [(2304, 768), (768, 768), (3072, 768), (768, 3072)] * 3), 134742016),
+    ("group", (12608, [(2304, 768), (1000, 768), (768, 3072)]), 134742016),     # one item the grouped kernel does not take
+    ("group", (4096, [(768, 1536), (768, 1000)]), 37896192),                    # 18 cut tiles, and 25165824 for the single call
+    ("group", (12608, [(768, 768)] * 50), 134742016),                           # 48 + 2 items: two launches
+    ("group", (5252, [(3072, 768), (768, 3072)] * 26), 134742016),
+    ("group", (1000, [(768, 768)] * 3), 0),                                     # under 1024 rows: single calls of 0 bytes
+    ("group", (12608, [(768, 768)] * 26), 0),                                   # 234 tiles: a last round >= 90 % full runs whole
+    ("group", (1024, [(768, 768)]), 4737024),                                   # 144 K-steps shared by 9 workgroups
+    ("ksplit", (192, 768, 50304), 16515072),
+    ("ksplit", (2624, 768, 50304), 0),
+    ("ksplit", (192, 768, 8192), 4718592),
+    ("ksplit", (192, 768, 8128), 0),                # K < 8192
+    ("ksplit", (2048, 768, 50304), 0),              # 192 tiles of 64 x 128
+    ("ksplit", (1984, 768, 50304), 12189696),       # 186 tiles
+    ("ksplit", (64, 128, 16384), 524288),
+]
+# ((M, N, K, epilogue, tile_hint), cfg, rows_a) of xfm_gemm_nt_plan, recorded from the same library
+GEMM_NT_PLAN_TABLE = [
+    ((12608, 768, 768, 0, 0), 5, 0), ((25216, 768, 768, 0, 0), 5, 21760), ((25216, 3072, 768, 2, 0), 5, 0), ((5248, 1536, 768, 0, 0), 1, 0),
+    ((2624, 768, 3072, 0, 0), 8, 0), ((192, 768, 50304, 4, 0), 7, 0), ((928, 768, 768, 0, 0), 3, 0), ((64, 64, 64, 0, 0), 3, 0),
+    ((12608, 768, 768, 0, 4), 4, 0),
+]
+NO_LIMIT = 2 ** 63 - 1
+# ((M, N, K, ldy, ldx, splits_hint, workspace bytes), kernel, splits, bytes used) of xfm_gemm_tn_plan (kernel 0 = 256 x 256, 1 = ring,
+# 2 = register-staged), derived from that library's xfm_gemm_tn: what it launched with a workspace of that size
+GEMM_TN_PLAN_TABLE = [
+    ((4096, 768, 1536, 768, 1536, 0, NO_LIMIT), 0, 8, 37748736),
+    ((4096, 768, 1536, 768, 1536, 0, 37748736), 0, 8, 37748736),
+    ((4096, 768, 1536, 768, 1536, 0, 37748735), 1, 6, 28311552),      # a byte short: steps down to the 128 x 128 plan
+    ((4096, 768, 1536, 768, 1536, 0, 28311552), 1, 6, 28311552),
+    ((4096, 768, 1536, 768, 1536, 0, 28311551), 1, 6, 0),             # ... and that one to atomics
+    ((4096, 768, 1536, 768, 1536, 0, 0), 1, 6, 0),
+    ((4096, 768, 1536, 768, 1536, -3, 0), 0, 8, 0),                   # forced 256 x 256 without a workspace: atomics
+    ((4096, 768, 1536, 768, 1536, -4, NO_LIMIT), 1, 6, 28311552),     # never the 256 x 256 kernel
+    ((4096, 768, 1536, 768, 1536, -5, NO_LIMIT), 2, 6, 28311552),
+    ((1920, 768, 768, 768, 768, 0, NO_LIMIT), 1, 4, 0),               # under the 16 MB floor
+    ((1920, 768, 768, 768, 768, 4, NO_LIMIT), 1, 4, 9437184),         # explicit splits use the planes whatever their size
+    ((1920, 768, 768, 768, 768, 1, NO_LIMIT), 1, 1, 0),
+    ((21624, 2304, 768, 2304, 768, 0, NO_LIMIT), 0, 9, 63700992),     # the body of the ragged split
+    ((21624, 2304, 768, 2304, 768, 0, 0), 1, 4, 0),                   # no workspace: all rows in one 128 x 128 call
+    ((4096, 1000, 768, 1000, 768, 0, NO_LIMIT), 2, 8, 25165824),
+    ((4096, 768, 1536, 1 << 21, 1536, 0, NO_LIMIT), 1, 6, 28311552),  # rows too far apart for the 256 x 256 kernel's 32-bit offsets
+]
+
+
+def test_gemm_workspace_and_plan_tables():
+    """xfm_gemm_tn_workspace / _batch_workspace / _group_workspace / xfm_gemm_nt_ksplit_workspace, xfm_gemm_nt_plan and xfm_gemm_tn_plan
+    over fixed tables, in a fresh process without XFM_* knobs (the child loads the library alone: no GPU, no torch)."""
+    import json
+    import subprocess
+    import sys
+    from xfm_amd import build
+    child = r"""
+import ctypes, json, sys
+lib = ctypes.CDLL(sys.argv[1])
+I, L, P = ctypes.c_int, ctypes.c_long, ctypes.c_void_p
+class Item(ctypes.Structure):
+    _fields_ = [("dY", P), ("ldy", L), ("X", P), ("ldx", L), ("dW", P), ("ldw", L), ("dbias", P), ("N", I), ("K", I)]
+sig = {"tn": ("xfm_gemm_tn_workspace", [I] * 3), "batch": ("xfm_gemm_tn_batch_workspace", [I] * 4),
+       "group": ("xfm_gemm_tn_group_workspace", [I, P, I]), "ksplit": ("xfm_gemm_nt_ksplit_workspace", [I] * 3)}
+for name, args in sig.values():
+    getattr(lib, name).restype, getattr(lib, name).argtypes = L, args
+lib.xfm_gemm_nt_plan.argtypes = [I] * 5 + [P] * 2
+lib.xfm_gemm_tn_plan.argtypes = [I] * 3 + [L] * 2 + [I, L] + [P] * 3
+ws, nt, tn = json.load(sys.stdin)
+out = [[], [], []]
+for kind, a in ws:
+    if kind == "group":   # dummy non-NULL, 16-byte aligned pointers: the query dereferences none of them
+        arr = (Item * len(a[1]))(*[Item(0x10000, N, 0x10000, K, 0x10000, K, None, N, K) for N, K in a[1]])
+        a = (len(a[1]), ctypes.addressof(arr), a[0])
+    out[0].append(getattr(lib, sig[kind][0])(*a))
+c, r, u = I(), I(), L()
+for a in nt:
+    assert lib.xfm_gemm_nt_plan(*a, ctypes.addressof(c), ctypes.addressof(r)) == 0
+    out[1].append([c.value, r.value])
+for a in tn:
+    assert lib.xfm_gemm_tn_plan(*a, ctypes.addressof(c), ctypes.addressof(r), ctypes.addressof(u)) == 0
+    out[2].append([c.value, r.value, u.value])
+print(json.dumps(out))
+"""
+    assert len(GEMM_WORKSPACE_TABLE) >= 25
+    e = {k: v for k, v in os.environ.items() if not k.startswith("XFM_")}
+    rows = [[(k, a) for k, a, _ in GEMM_WORKSPACE_TABLE], [a for a, _, _ in GEMM_NT_PLAN_TABLE], [a for a, _, _, _ in GEMM_TN_PLAN_TABLE]]
+    r = subprocess.run([sys.executable, "-c", child, build.build()], input=json.dumps(rows), env=e, capture_output=True, text=True, check=True)
+    ws, nt, tn = json.loads(r.stdout)
+    assert ws == [w for _, _, w in GEMM_WORKSPACE_TABLE], [(row, got) for row, got in zip(GEMM_WORKSPACE_TABLE, ws) if got != row[2]]
+    assert nt == [[c, ra] for _, c, ra in GEMM_NT_PLAN_TABLE], nt
+    assert tn == [[k, s, u] for _, k, s, u in GEMM_TN_PLAN_TABLE], tn

@@ -144,6 +144,27 @@ def test_gemm_tn_wgrad_accumulates(M, N, K, splits):
     _close(db, dy.float().sum(0) + 1.0, 2e-4, "bias grad fused into wgrad")
 
 
+def test_gemm_tn_with_less_workspace_than_the_query_asks_for():
+    """A caller that brings less workspace than xfm_gemm_tn_workspace asks for gets the same gradient by the next route down: the
+    256 x 256 kernel with all 37748736 bytes, the 128 x 128 plan with the 28311552 that one needs, fp32 atomics with none (hint 0
+    each time; through the C ABI, functional.gemm_tn always brings what the plan asks for)."""
+    from xfm_amd import _lib
+    M, N, K = 4096, 768, 1536
+    lib = _lib.load()
+    assert lib.xfm_gemm_tn_workspace(M, N, K) == 37748736
+    dy, x = _rand((M, N), seed=10), _rand((M, K), seed=11)
+    ref, ref_b = dy.float().t() @ x.float() + 1.0, dy.float().sum(0) + 1.0
+    stream = torch.cuda.current_stream().cuda_stream
+    for nbytes in (37748736, 28311552, 0):
+        dw = torch.ones((N, K), dtype=F32, device="cuda")
+        db = torch.ones((N,), dtype=F32, device="cuda")
+        ws = torch.empty(nbytes // 4, dtype=F32, device="cuda") if nbytes else None
+        _lib.check(lib.xfm_gemm_tn(dy.data_ptr(), N, x.data_ptr(), K, dw.data_ptr(), K, db.data_ptr(), M, N, K, 0,
+                                   ws.data_ptr() if nbytes else None, nbytes, stream), "gemm_tn")
+        _close(dw, ref, 2e-4, f"wgrad, {nbytes} bytes of workspace")
+        _close(db, ref_b, 2e-4, f"bias grad, {nbytes} bytes of workspace")
+
+
 def test_gemm_tn_exact_integers_catch_layout_errors():
     Fx = _fx()
     M, N, K = 128, 128, 128

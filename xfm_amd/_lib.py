@@ -13,7 +13,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # XFM_HIP_LIB: A/B a differently built library (kernel experiments); the default is the in-tree build.
 LIB_PATH = os.environ.get("XFM_HIP_LIB") or os.path.join(_HERE, "libxfm_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 c_void_p, c_int, c_long, c_float, c_u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_uint32
 
@@ -130,6 +130,8 @@ SIGNATURES = {
     "xfm_gemm_nt_ksplit": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
                                    c_long, c_void_p]),
     "xfm_gemm_tn_workspace": (c_long, [c_int, c_int, c_int]),
+    "xfm_gemm_tn_plan": (c_int, [c_int, c_int, c_int, c_long, c_long, c_int, c_long, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                 ctypes.POINTER(c_long)]),
     "xfm_gemm_tn": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int,
                             c_void_p, c_long, c_void_p]),
     "xfm_cast_transpose": (c_int, [c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p]),

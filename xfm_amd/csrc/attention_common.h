@@ -276,12 +276,3 @@ static void attn_geom(int S, int& nw, int& blocks, int max_nw = 8) {
   blocks = cdiv(tiles, nw);
   nw = cdiv(tiles, blocks);
 }
-
-// Every attention launch with dynamic LDS: MaxLds is the most this kernel instantiation is ever launched with; its first launch
-// raises the instantiation's limit to that (the default stops at 64 KB), one guard per instantiation.
-template <auto Kernel, int MaxLds, typename... Args>
-static void attn_launch(dim3 grid, dim3 blk, size_t lds, hipStream_t st, const Args&... args) {
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MaxLds);
-  (void)attr;
-  hipLaunchKernelGGL(Kernel, grid, blk, lds, st, args...);
-}

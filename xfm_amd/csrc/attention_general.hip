@@ -504,11 +504,11 @@ static int launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
   const dim3 grid(blocks, a.H, a.B), blk(nw * 64);
   const size_t lds = attn_lds_bytes(a.Sk, nw, 0);
   if (attn_resident(a.Sk, nw)) {
-    if (attn_plain(a)) attn_launch<attn_fwd_kernel<true, true>, ATTN_RES_LDS>(grid, blk, lds, st, a);
-    else attn_launch<attn_fwd_kernel<true, false>, ATTN_RES_LDS>(grid, blk, lds, st, a);
+    if (attn_plain(a)) lds_launch<attn_fwd_kernel<true, true>, ATTN_RES_LDS>(grid, blk, lds, st, a);
+    else lds_launch<attn_fwd_kernel<true, false>, ATTN_RES_LDS>(grid, blk, lds, st, a);
   } else {
-    if (attn_plain(a)) attn_launch<attn_fwd_kernel<false, true>, ATTN_STREAM_LDS>(grid, blk, lds, st, a);
-    else attn_launch<attn_fwd_kernel<false, false>, ATTN_STREAM_LDS>(grid, blk, lds, st, a);
+    if (attn_plain(a)) lds_launch<attn_fwd_kernel<false, true>, ATTN_STREAM_LDS>(grid, blk, lds, st, a);
+    else lds_launch<attn_fwd_kernel<false, false>, ATTN_STREAM_LDS>(grid, blk, lds, st, a);
   }
   return xfm_check_launch("attn_fwd");
 }
@@ -532,13 +532,13 @@ static int launch_attn_bwd_dq(const AttnArgs& a, int nw, int blocks, int sums_nb
   const dim3 grid(blocks, a.H, sums_nb > 0 ? cdiv(a.B, sums_nb) : a.B), blk(nw * 64);
   const bool plain = attn_plain(a);
   if (sums_nb > 0) {
-    attn_launch<attn_bwd_dq_kernel<4, true, true>, ATTN_RES_LDS>(grid, blk, attn_lds_bytes(a.Sk, nw, 8 * 4096), st, a, sums_nb);
+    lds_launch<attn_bwd_dq_kernel<4, true, true>, ATTN_RES_LDS>(grid, blk, attn_lds_bytes(a.Sk, nw, 8 * 4096), st, a, sums_nb);
   } else if (attn_resident(a.Sk, nw)) {
-    if (plain) attn_launch<attn_bwd_dq_kernel<0, true, true>, ATTN_RES_LDS>(grid, blk, attn_lds_bytes(a.Sk, nw, 0), st, a, 1);
-    else attn_launch<attn_bwd_dq_kernel<0, true, false>, ATTN_RES_LDS>(grid, blk, attn_lds_bytes(a.Sk, nw, 0), st, a, 1);
+    if (plain) lds_launch<attn_bwd_dq_kernel<0, true, true>, ATTN_RES_LDS>(grid, blk, attn_lds_bytes(a.Sk, nw, 0), st, a, 1);
+    else lds_launch<attn_bwd_dq_kernel<0, true, false>, ATTN_RES_LDS>(grid, blk, attn_lds_bytes(a.Sk, nw, 0), st, a, 1);
   } else {
-    if (plain) attn_launch<attn_bwd_dq_kernel<0, false, true>, ATTN_STREAM_LDS>(grid, blk, attn_lds_bytes(a.Sk, nw, 0), st, a, 1);
-    else attn_launch<attn_bwd_dq_kernel<0, false, false>, ATTN_STREAM_LDS>(grid, blk, attn_lds_bytes(a.Sk, nw, 0), st, a, 1);
+    if (plain) lds_launch<attn_bwd_dq_kernel<0, false, true>, ATTN_STREAM_LDS>(grid, blk, attn_lds_bytes(a.Sk, nw, 0), st, a, 1);
+    else lds_launch<attn_bwd_dq_kernel<0, false, false>, ATTN_STREAM_LDS>(grid, blk, attn_lds_bytes(a.Sk, nw, 0), st, a, 1);
   }
   return xfm_check_launch("attn_bwd_dq");
 }
@@ -550,11 +550,11 @@ static int launch_attn_bwd_dkv(const AttnArgs& a, hipStream_t st) {
   const bool plain = attn_plain(a);
   static const bool dkv_res = xfm_env_flag("XFM_ATTN_DKV_RES", true);  // tuning knob
   if (dkv_res && attn_resident(a.Sq, nw)) {
-    if (plain) attn_launch<attn_bwd_dkv_kernel<true, true>, ATTN_RES_LDS>(grid, blk, attn_lds_bytes(a.Sq, nw, 0), st, a);
-    else attn_launch<attn_bwd_dkv_kernel<true, false>, ATTN_RES_LDS>(grid, blk, attn_lds_bytes(a.Sq, nw, 0), st, a);
+    if (plain) lds_launch<attn_bwd_dkv_kernel<true, true>, ATTN_RES_LDS>(grid, blk, attn_lds_bytes(a.Sq, nw, 0), st, a);
+    else lds_launch<attn_bwd_dkv_kernel<true, false>, ATTN_RES_LDS>(grid, blk, attn_lds_bytes(a.Sq, nw, 0), st, a);
   } else {
-    if (plain) attn_launch<attn_bwd_dkv_kernel<false, true>, ATTN_STREAM_LDS>(grid, blk, 2 * ATTN_SLOT, st, a);
-    else attn_launch<attn_bwd_dkv_kernel<false, false>, ATTN_STREAM_LDS>(grid, blk, 2 * ATTN_SLOT, st, a);
+    if (plain) lds_launch<attn_bwd_dkv_kernel<false, true>, ATTN_STREAM_LDS>(grid, blk, 2 * ATTN_SLOT, st, a);
+    else lds_launch<attn_bwd_dkv_kernel<false, false>, ATTN_STREAM_LDS>(grid, blk, 2 * ATTN_SLOT, st, a);
   }
   return xfm_check_launch("attn_bwd_dkv");
 }

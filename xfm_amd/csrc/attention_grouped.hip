@@ -687,7 +687,7 @@ static int launch_xattn_fwd_packed(const AttnArgs& a, hipStream_t st) {
   const int tq = cdiv(a.Sq, 16);
   int rpb = 8 / tq < ATTN_RES_MAX ? 8 / tq : ATTN_RES_MAX;
   if (rpb > a.B) rpb = a.B;
-  attn_launch<xattn_fwd_kernel<true, false, false>, XATTN_LDS>(dim3(1, a.H, cdiv(a.B, rpb)), dim3(rpb * tq * 64), (size_t)rpb * ATTN_SLOT, st, a);
+  lds_launch<xattn_fwd_kernel<true, false, false>, XATTN_LDS>(dim3(1, a.H, cdiv(a.B, rpb)), dim3(rpb * tq * 64), (size_t)rpb * ATTN_SLOT, st, a);
   return xfm_check_launch("xattn_fwd<pack>");
 }
 
@@ -697,15 +697,15 @@ static bool xattn_streamed(const AttnArgs& a) { return a.Sk > 64 * ATTN_RES_MAX;
 static int launch_xattn_fwd(const AttnArgs& a, hipStream_t st) {
   const dim3 grid(1, a.H, a.n_groups), blk(512);
   if (xattn_streamed(a)) {
-    attn_launch<xattn_fwd_stream_kernel, XS_LDS>(grid, blk, XS_LDS, st, a);
+    lds_launch<xattn_fwd_stream_kernel, XS_LDS>(grid, blk, XS_LDS, st, a);
     return xfm_check_launch("xattn_fwd_stream");
   }
   const bool mask = a.key_keep != nullptr, drop = a.drop_thresh != 0u;
   const size_t lds = (size_t)cdiv(a.Sk, 64) * ATTN_SLOT + 1024;
-  if (mask && drop) attn_launch<xattn_fwd_kernel<false, true, true>, XATTN_LDS>(grid, blk, lds, st, a);
-  else if (mask) attn_launch<xattn_fwd_kernel<false, true, false>, XATTN_LDS>(grid, blk, lds, st, a);
-  else if (drop) attn_launch<xattn_fwd_kernel<false, false, true>, XATTN_LDS>(grid, blk, lds, st, a);
-  else attn_launch<xattn_fwd_kernel<false, false, false>, XATTN_LDS>(grid, blk, lds, st, a);
+  if (mask && drop) lds_launch<xattn_fwd_kernel<false, true, true>, XATTN_LDS>(grid, blk, lds, st, a);
+  else if (mask) lds_launch<xattn_fwd_kernel<false, true, false>, XATTN_LDS>(grid, blk, lds, st, a);
+  else if (drop) lds_launch<xattn_fwd_kernel<false, false, true>, XATTN_LDS>(grid, blk, lds, st, a);
+  else lds_launch<xattn_fwd_kernel<false, false, false>, XATTN_LDS>(grid, blk, lds, st, a);
   return xfm_check_launch("xattn_fwd");
 }
 
@@ -713,11 +713,11 @@ static int launch_xattn_dq(const AttnArgs& a, hipStream_t st) {
   const dim3 grid(1, a.H, a.n_groups), blk(512);
   const bool mask = a.key_keep != nullptr, drop = a.drop_thresh != 0u;
   const size_t lds = (size_t)cdiv(a.Sk, 64) * ATTN_SLOT + 1024;
-  if (xattn_streamed(a)) attn_launch<xattn_dq_stream_kernel, XS_LDS>(grid, blk, XS_LDS, st, a);
-  else if (mask && drop) attn_launch<xattn_dq_kernel<true, true>, XATTN_LDS>(grid, blk, lds, st, a);
-  else if (mask) attn_launch<xattn_dq_kernel<true, false>, XATTN_LDS>(grid, blk, lds, st, a);
-  else if (drop) attn_launch<xattn_dq_kernel<false, true>, XATTN_LDS>(grid, blk, lds, st, a);
-  else attn_launch<xattn_dq_kernel<false, false>, XATTN_LDS>(grid, blk, lds, st, a);
+  if (xattn_streamed(a)) lds_launch<xattn_dq_stream_kernel, XS_LDS>(grid, blk, XS_LDS, st, a);
+  else if (mask && drop) lds_launch<xattn_dq_kernel<true, true>, XATTN_LDS>(grid, blk, lds, st, a);
+  else if (mask) lds_launch<xattn_dq_kernel<true, false>, XATTN_LDS>(grid, blk, lds, st, a);
+  else if (drop) lds_launch<xattn_dq_kernel<false, true>, XATTN_LDS>(grid, blk, lds, st, a);
+  else lds_launch<xattn_dq_kernel<false, false>, XATTN_LDS>(grid, blk, lds, st, a);
   return xfm_check_launch("xattn_dq");
 }
 
@@ -727,7 +727,7 @@ static int launch_xattn_dkv(const AttnArgs& a, hipStream_t st) {
   static const int dkv_nw = xfm_env_int("XFM_XATTN_DKV_NW", 16);  // tuning knob: waves (16-key tiles) per workgroup
   attn_geom(a.Sk, nw, blocks, dkv_nw);
   const dim3 grid(blocks, a.H, a.n_groups), blk(nw * 64);
-  if (a.drop_thresh != 0u) attn_launch<xattn_dkv_kernel<true>, XATTN_LDS>(grid, blk, XATTN_LDS, st, a);
-  else attn_launch<xattn_dkv_kernel<false>, XATTN_LDS>(grid, blk, XATTN_LDS, st, a);
+  if (a.drop_thresh != 0u) lds_launch<xattn_dkv_kernel<true>, XATTN_LDS>(grid, blk, XATTN_LDS, st, a);
+  else lds_launch<xattn_dkv_kernel<false>, XATTN_LDS>(grid, blk, XATTN_LDS, st, a);
   return xfm_check_launch("xattn_dkv");
 }

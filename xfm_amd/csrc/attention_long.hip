@@ -587,9 +587,9 @@ static int launch_attn_bwd_long_dq(const AttnArgs& a, hipStream_t st) {
   const int qblocks = cdiv(a.Sq, 256);
   const dim3 grid(qblocks * a.H * a.B), blk(512);
   constexpr int lds_b = LB_RING * LB_SLOT_DQ;
-  if (long_tiled(a, a.bias_tiled)) attn_launch<attn_bwd_dq_long_kernel<true, true>, lds_b>(grid, blk, lds_b, st, a, qblocks);
-  else if (a.bias != nullptr) attn_launch<attn_bwd_dq_long_kernel<true, false>, lds_b>(grid, blk, lds_b, st, a, qblocks);
-  else attn_launch<attn_bwd_dq_long_kernel<false, false>, lds_b>(grid, blk, lds_b, st, a, qblocks);
+  if (long_tiled(a, a.bias_tiled)) lds_launch<attn_bwd_dq_long_kernel<true, true>, lds_b>(grid, blk, lds_b, st, a, qblocks);
+  else if (a.bias != nullptr) lds_launch<attn_bwd_dq_long_kernel<true, false>, lds_b>(grid, blk, lds_b, st, a, qblocks);
+  else lds_launch<attn_bwd_dq_long_kernel<false, false>, lds_b>(grid, blk, lds_b, st, a, qblocks);
   return xfm_check_launch("attn_bwd_dq_long");
 }
 
@@ -598,7 +598,7 @@ static int launch_attn_bwd_long_dq(const AttnArgs& a, hipStream_t st) {
 static int launch_attn_dbias_blocks(const AttnArgs& a, int slices, hipStream_t st) {
   const int qb = cdiv(a.Sq, 128), kb = cdiv(a.Sk, 128);
   float* planes = slices > 1 ? a.dbias_ws : nullptr;
-  attn_launch<attn_dbias_long_kernel<true>, 2 * LD_STAGE>(dim3(qb * kb * slices * a.H), dim3(512), 2 * LD_STAGE, st, a, qb, kb, slices, planes);
+  lds_launch<attn_dbias_long_kernel<true>, 2 * LD_STAGE>(dim3(qb * kb * slices * a.H), dim3(512), 2 * LD_STAGE, st, a, qb, kb, slices, planes);
   return xfm_check_launch("attn_dbias_long");
 }
 
@@ -606,8 +606,8 @@ static int launch_attn_bwd_long_dkv(const AttnArgs& a, hipStream_t st) {
   const int kblocks = cdiv(a.Sk, 256);
   const dim3 grid(kblocks * a.H * a.B), blk(512);
   constexpr int lds_b = LB_RING * LB_SLOT_DKV;
-  if (long_tiled(a, a.bias_t_tiled)) attn_launch<attn_bwd_dkv_long_kernel<true, true>, lds_b>(grid, blk, lds_b, st, a, kblocks);
-  else if (a.bias != nullptr) attn_launch<attn_bwd_dkv_long_kernel<true, false>, lds_b>(grid, blk, lds_b, st, a, kblocks);
-  else attn_launch<attn_bwd_dkv_long_kernel<false, false>, lds_b>(grid, blk, lds_b, st, a, kblocks);
+  if (long_tiled(a, a.bias_t_tiled)) lds_launch<attn_bwd_dkv_long_kernel<true, true>, lds_b>(grid, blk, lds_b, st, a, kblocks);
+  else if (a.bias != nullptr) lds_launch<attn_bwd_dkv_long_kernel<true, false>, lds_b>(grid, blk, lds_b, st, a, kblocks);
+  else lds_launch<attn_bwd_dkv_long_kernel<false, false>, lds_b>(grid, blk, lds_b, st, a, kblocks);
   return xfm_check_launch("attn_bwd_dkv_long");
 }

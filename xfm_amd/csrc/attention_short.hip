@@ -737,9 +737,9 @@ template <int NP, bool PRE, bool DBG = false>
 static void attn_short_dq_launch(dim3 grid, hipStream_t st, const AttnArgs& a, int nb, int groups, long long* dbg = nullptr) {
   constexpr int lds = PRE && NP <= 7 ? VB_LDS_QL(3, NP) : VB_LDS(3);
 #ifdef XFM_DIAG
-  attn_launch<attn_bwd_dq_short_kernel<3, NP, PRE, DBG>, lds>(grid, dim3(768), lds, st, a, nb, groups, dbg);   // (DBG = false ignores dbg)
+  lds_launch<attn_bwd_dq_short_kernel<3, NP, PRE, DBG>, lds>(grid, dim3(768), lds, st, a, nb, groups, dbg);   // (DBG = false ignores dbg)
 #else
-  attn_launch<attn_bwd_dq_short_kernel<3, NP, PRE>, lds>(grid, dim3(768), lds, st, a, nb, groups);
+  lds_launch<attn_bwd_dq_short_kernel<3, NP, PRE>, lds>(grid, dim3(768), lds, st, a, nb, groups);
 #endif
 }
 // dQ, delta and the bias gradient: into the planes of a.dbias_ws when there is one, else by float atomics into dbias.
@@ -766,7 +766,7 @@ static int launch_attn_bwd_dkv_short(const AttnArgs& a, hipStream_t st) {
   int groups;
   const int nb = attn_short_nb(a, a.Sk, VK_KT, groups);
   const dim3 grid(groups * a.H * cdiv(a.B, nb)), blk(VK_KT * 256);
-  if (a.Sq <= 128) attn_launch<attn_bwd_dkv_short_kernel<4>, VK_LDS(4)>(grid, blk, VK_LDS(4), st, a, nb, groups);
-  else attn_launch<attn_bwd_dkv_short_kernel<7>, VK_LDS(7)>(grid, blk, VK_LDS(7), st, a, nb, groups);
+  if (a.Sq <= 128) lds_launch<attn_bwd_dkv_short_kernel<4>, VK_LDS(4)>(grid, blk, VK_LDS(4), st, a, nb, groups);
+  else lds_launch<attn_bwd_dkv_short_kernel<7>, VK_LDS(7)>(grid, blk, VK_LDS(7), st, a, nb, groups);
   return xfm_check_launch("attn_bwd_dkv_short");
 }

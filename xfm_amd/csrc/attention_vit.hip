@@ -230,14 +230,14 @@ static int launch_attn_fwd_vit(const AttnArgs& a, hipStream_t st) {
   const dim3 grid(vm.grid), blk(VF_NW * 64);
   const bool k13 = cdiv(a.Sq, 16) == 13;
   if (a.bias == nullptr) {
-    if (k13) attn_launch<attn_fwd_vit_kernel<false, 13, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
-    else attn_launch<attn_fwd_vit_kernel<false, 0, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
+    if (k13) lds_launch<attn_fwd_vit_kernel<false, 13, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
+    else lds_launch<attn_fwd_vit_kernel<false, 0, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
   } else if (a.bias_tiled != nullptr) {
-    if (k13) attn_launch<attn_fwd_vit_kernel<true, 13, true>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
-    else attn_launch<attn_fwd_vit_kernel<true, 0, true>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
+    if (k13) lds_launch<attn_fwd_vit_kernel<true, 13, true>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
+    else lds_launch<attn_fwd_vit_kernel<true, 0, true>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
   } else {
-    if (k13) attn_launch<attn_fwd_vit_kernel<true, 13, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
-    else attn_launch<attn_fwd_vit_kernel<true, 0, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
+    if (k13) lds_launch<attn_fwd_vit_kernel<true, 13, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
+    else lds_launch<attn_fwd_vit_kernel<true, 0, false>, VF_LDS>(grid, blk, VF_LDS, st, a, vm);
   }
   return xfm_check_launch("attn_fwd_vit");
 }
@@ -609,8 +609,8 @@ static bool attn_vit3_shape(const AttnArgs& a, int mode) {
 static int launch_attn_bwd_vit3(const AttnArgs& a, hipStream_t st) {
   const VitMap vm = vit_map(a.B, a.H);
   const dim3 grid(vm.grid), blk(512);
-  if (a.bias != nullptr && a.dbias != nullptr) attn_launch<attn_bwd_vit3_kernel<true, true>, V3_LDS>(grid, blk, V3_LDS, st, a, vm);
-  else if (a.bias != nullptr) attn_launch<attn_bwd_vit3_kernel<true, false>, V3_LDS>(grid, blk, V3_LDS, st, a, vm);
-  else attn_launch<attn_bwd_vit3_kernel<false, false>, V3_LDS>(grid, blk, V3_LDS, st, a, vm);
+  if (a.bias != nullptr && a.dbias != nullptr) lds_launch<attn_bwd_vit3_kernel<true, true>, V3_LDS>(grid, blk, V3_LDS, st, a, vm);
+  else if (a.bias != nullptr) lds_launch<attn_bwd_vit3_kernel<true, false>, V3_LDS>(grid, blk, V3_LDS, st, a, vm);
+  else lds_launch<attn_bwd_vit3_kernel<false, false>, V3_LDS>(grid, blk, V3_LDS, st, a, vm);
   return xfm_check_launch("attn_bwd_vit3");
 }

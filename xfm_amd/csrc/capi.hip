@@ -64,6 +64,10 @@ int xfm_gemm_nt_ksplit(const xfm_bf16* A, long lda, const xfm_bf16* B, long ldb,
   return xfm_gemm_nt_ksplit_impl(A, lda, B, ldb, out, ldo, out_bf16, bias, M, N, K, workspace, workspace_bytes, ST(stream));
 }
 long xfm_gemm_tn_workspace(int M, int N, int K) { return xfm_gemm_tn_workspace_impl(M, N, K); }
+int xfm_gemm_tn_plan(int M, int N, int K, long ldy, long ldx, int splits_hint, long workspace_bytes, int* kernel, int* splits,
+                     long* workspace_used) {
+  return xfm_gemm_tn_plan_impl(M, N, K, ldy, ldx, splits_hint, workspace_bytes, kernel, splits, workspace_used);
+}
 
 int xfm_gemm_tn(const xfm_bf16* dY, long ldy, const xfm_bf16* X, long ldx, float* dW, long ldw, float* dbias, int M, int N,
                 int K, int splits_hint, float* workspace, long workspace_bytes, void* stream) {

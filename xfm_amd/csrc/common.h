@@ -126,4 +126,13 @@ __device__ __forceinline__ void grouped_tile(int wg, int tiles_m, int tiles_n, i
   tm = first + in % gm;
   tn = in / gm;
 }
+
+// Every launch with dynamic LDS (GEMM and attention): MaxLds is the most this kernel instantiation is ever launched with; its first
+// launch raises the instantiation's limit to that (the default stops at 64 KB), one guard per instantiation.
+template <auto Kernel, int MaxLds, typename... Args>
+static void lds_launch(dim3 grid, dim3 blk, size_t lds, hipStream_t st, const Args&... args) {
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MaxLds);
+  (void)attr;
+  hipLaunchKernelGGL(Kernel, grid, blk, lds, st, args...);
+}
 #endif

@@ -98,6 +98,9 @@ def deterministic():
     return os.environ.get("XFM_DETERMINISTIC", "0") not in ("", "0")
 
 
+_NO_LIMIT = 2 ** 63 - 1   # LONG_MAX: xfm_gemm_tn_plan's "as much workspace as the plan wants"
+
+
 def gemm_tn(dy, x, dw, n=None, splits=0, dbias=None):
     """dw[N,K] (fp32) += dy[M,N]^T @ x[M,K]; optionally dbias[N] (fp32) += dy.sum(0) in the same pass."""
     _dev(dy)
@@ -110,8 +113,10 @@ def gemm_tn(dy, x, dw, n=None, splits=0, dbias=None):
         colsum(dy, dbias, N)
         dbias = None
     lib = _lib.load()
-    need = lib.xfm_gemm_tn_workspace(M, N, K) if splits == 0 else (splits * ((N + 127) // 128) * ((K + 127) // 128) * 65536 if splits > 1 else 0)
-    ws = workspace(need, dy.device) if need > 0 else None
+    # the workspace this call's plan writes through (the negative hints, kernel A/B switches, keep running without one: atomics)
+    kernel, nsplit, need = ctypes.c_int(), ctypes.c_int(), ctypes.c_long()
+    check(lib.xfm_gemm_tn_plan(M, N, K, dy.stride(0), x.stride(0), splits, _NO_LIMIT if splits >= 0 else 0, kernel, nsplit, need), "gemm_tn_plan")
+    ws = workspace(need.value, dy.device) if need.value > 0 else None
     check(lib.xfm_gemm_tn(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dw.data_ptr(), dw.stride(0), _ptr(dbias), M, N, K,
                           splits, _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()), "gemm_tn")
 
