@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 12
+#define XFM_ABI_VERSION 13
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -480,6 +480,25 @@ int xfm_ce_soft_fwd(const float* logits, long ld, const float* target, long ldt,
 int xfm_ce_soft_bwd(const float* logits, long ld, const float* target, long ldt, int R, int V, const float* lse, const float* tsum,
                     const float* scale, int per_row_scale, xfm_bf16* dlogits, long ldd, void* stream);
 
+/* ---- Evaluation step of the ImageNet loop (Imagenet.py:495-536 evaluate; ABI 13) --------------------------------------------------------
+ * One pass over fp32 logits [R, ld >= V] (ld need NOT be a multiple of 4 and the base need not be aligned: 16-byte loads are used when
+ * every row starts on 16 bytes, scalar loads otherwise), labels int64 [R].  Per row r:
+ *   row_loss[r] = logsumexp(x) - x[label]                                  (CrossEntropyLoss, reduction 'none')
+ *   row_rank[r] = #{j: x[j] > x[label]} + #{j < label: x[j] == x[label]}   (int32)
+ * THE TIE RULE: the rank is the label's position in a STABLE descending sort of the row -- of equal logits the lower column comes
+ * first.  torch.topk leaves the order of ties unspecified; this library pins it.  The label is among the top k iff row_rank < k.
+ * A trailing single workgroup then ADDS into acc (fp32 [3]), the rows one after the other in ascending order, no atomics:
+ *   acc[0] += sum_r row_loss[r],   acc[1] += #{r: row_rank[r] < k1},   acc[2] += #{r: row_rank[r] < k2}.
+ * The counts are exact in fp32 (up to 2^24 rows per buffer) and the result is bit-reproducible with and without XFM_DETERMINISTIC.  acc
+ * accumulates across calls: zero it once per evaluation, read it once at the end.
+ * A label outside [0, V) is the caller's error (the Python wrapper refuses it where it can see the labels on the host); in the kernel
+ * such a row contributes nothing to acc, and gets row_loss 0 and row_rank V.
+ * row_loss and row_rank may each be NULL.  The library owns no scratch memory, so with either NULL one workgroup walks all rows itself
+ * (same order, same arithmetic, same bits; slower -- pass both for large R).
+ * XFM_E_ARG (nothing is launched): k1 < 1, k2 < k1, k2 > V, ld < V, R < 1, or a NULL logits / labels / acc. */
+int xfm_ce_topk_eval(const float* logits, long ld, int R, int V, const int64_t* labels, int k1, int k2, float* row_loss, int* row_rank,
+                     float* acc, void* stream);
+
 /* ---- Device Mixup / CutMix (timm Mixup._mix_batch / _mix_elem and mixup_target as called at Imagenet.py:468-469; ABI 10) -------------
  * xfm_mixup: fp32 images [B, C, H, W], B even, mixed IN PLACE: row i against the original row j = B - 1 - i, with the per-row device
  * arrays lam fp32 [B] and box int32 [B, 4] = (yl, yh, xl, xh).  lam_i == 1: row i is left alone; an empty box (yh <= yl or xh <= xl):
@@ -523,6 +542,11 @@ typedef struct {
   int zero_grad;              /* != 0: g is zeroed in the same sweep (the step's optimizer.zero_grad(): one pass over the arena less) */
 } xfm_adamw_args;
 int xfm_adamw(const xfm_adamw_args* a, void* stream);
+/* The same sweep with torch.optim.AdamW's single-tensor rule (non-amsgrad; Imagenet.py:569-570 builds that optimizer; ABI 13).  Same
+ * struct, same meaning of bc1 / bc2 / group / lr / wd / clip_coef / zero_grad, same 256-multiple length rule.  Per element, in this order:
+ *   g' = g * clip;  p *= 1 - lr * wd;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g' g';  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ * (xfm_adamw, the transformers rule: eps is added BEFORE the bias correction and the decay follows the update). */
+int xfm_adamw_torch(const xfm_adamw_args* a, void* stream);
 /* out[0] += sum x[i]^2 (n % 4 == 0), bit-reproducible: fixed-grid block partials through `workspace`
  * (XFM_SUMSQ_WORKSPACE_FLOATS floats, contents irrelevant) summed in a fixed order -- the clip coefficient derived from it must be
  * identical on every data-parallel rank (apex_ddp_accelerator.py:100-110 clips after the all-reduce). */

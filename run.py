@@ -2,6 +2,7 @@
 --master_port) -> one process per GPU on this node.
 
     python3 run.py --task pretrain_DIY --dist 1 --config configs/Pretrain_synthetic.yaml --output_dir output/pt
+    python3 run.py --task imagenet --dist gpu0 --config configs/Imagenet_synthetic.yaml --output_dir output/in
 
 `--dist` follows run.py:44-75: '1' / 'all' = every visible GPU of this node, 'f4' / 'l4' = the first / last four, 'gpuK' = GPU K
 alone.  The reference builds a `torch.distributed.launch --use_env` shell line and hands it to os.system; here the ranks are started
@@ -18,8 +19,8 @@ if ROOT not in sys.path:
 
 from xfm_amd.launch import launch, launch_command, visible_gpu_count  # noqa: E402
 
-TASK_SCRIPTS = {"pretrain_DIY": "Pretrain.py"}
-DEFAULT_CONFIGS = {"pretrain_DIY": "configs/Pretrain_synthetic.yaml"}
+TASK_SCRIPTS = {"pretrain_DIY": "Pretrain.py", "imagenet": "Imagenet.py"}
+DEFAULT_CONFIGS = {"pretrain_DIY": "configs/Pretrain_synthetic.yaml", "imagenet": "configs/Imagenet_synthetic.yaml"}
 
 
 def get_dist(args, n_visible=None):
@@ -46,9 +47,12 @@ def task_command(args, n_visible=None):
     if not args.config or not os.path.exists(args.config):
         args.config = os.path.join(ROOT, DEFAULT_CONFIGS[args.task])
     nproc, vis = get_dist(args, n_visible)
-    script_args = ["--seed", args.seed, "--epoch", args.epoch, "--config", args.config, "--output_dir", args.output_dir]
-    if args.bs > 0:
-        script_args += ["--bs", max(args.bs // nproc, 1)]  # "for each gpu, batch_size = bs // num_gpus" (run.py:362-363)
+    if args.task == "imagenet":   # run.py:275-287: no --bs, no --epoch
+        script_args = ["--config", args.config, "--output_dir", args.output_dir, "--seed", args.seed]
+    else:
+        script_args = ["--seed", args.seed, "--epoch", args.epoch, "--config", args.config, "--output_dir", args.output_dir]
+        if args.bs > 0:
+            script_args += ["--bs", max(args.bs // nproc, 1)]  # "for each gpu, batch_size = bs // num_gpus" (run.py:362-363)
     if args.checkpoint:
         script_args += ["--checkpoint", args.checkpoint]
     return launch_command(os.path.join(ROOT, TASK_SCRIPTS[args.task]), script_args, nproc, args.master_port), nproc, vis, script_args

@@ -582,9 +582,10 @@ class RCCLDDPAccelerator(Accelerator):
                 runs[-1][1] = b
             else:
                 runs.append([a, b, t[u]])
+        rule = adamw_rule(optimizer)
         for a, b, step in runs:
             Fx.adamw(arena.data[a:b], arena.grad[a:b], self._m[a:b], self._v[a:b], self._group[a // 256:(b + 255) // 256],
-                     lrs, wds, b1, b2, groups[0]["eps"], step, clip_coef)
+                     lrs, wds, b1, b2, groups[0]["eps"], step, clip_coef, rule=rule)
 
     # ---- the moments live in flat arenas; torch's optimizer.state_dict() / load_state_dict() see them as ordinary AdamW state ----
     def _hook_optimizer(self, optimizer):
@@ -670,3 +671,16 @@ class RCCLDDPAccelerator(Accelerator):
 
 def _is_adamw(opt):
     return type(opt).__name__ in ("AdamW",)
+
+
+def adamw_rule(opt):
+    """Which update an `AdamW` object stands for.  The class name does not say: optim.py's optimizer is transformers' rule (eps before the
+    bias correction, decay after the update -- xfm_adamw), Imagenet.py:569-570's is torch.optim.AdamW's own (decay first, eps after the
+    correction -- xfm_adamw_torch).  The builder says so with `adamw_rule="torch"` in the optimizer's `defaults` (or its first param
+    group; imagenet_loop.create_optimizer sets both); without the marker the transformers rule runs, as it always has."""
+    rule = getattr(opt, "defaults", {}).get("adamw_rule")
+    if rule is None and opt.param_groups:
+        rule = opt.param_groups[0].get("adamw_rule")
+    if rule not in (None, "torch", "transformers"):
+        raise ValueError(f"adamw_rule == {rule!r} (expected 'torch' or 'transformers')")
+    return rule or "transformers"

@@ -229,7 +229,9 @@ class ParamArena:
             p._xfm_arena = self
             self.offsets[id(p)] = (o, n)
             if p.requires_grad:  # gradients that arrive through autograd's AccumulateGrad (e.g. the ITC temperature)
-                p.register_hook(lambda g, _p=p: self.touch(_p))
+                # (autograd also calls the hook with None when a custom Function returns no gradient for an input it never used --
+                # the vision tower's mask_token in a pass without masks: that is `grad is None` in the reference, not a gradient)
+                p.register_hook(lambda g, _p=p: self.touch(_p) if g is not None else None)
         self.names = {id(p): name for name, p in params}
         for s in self.slots:
             s._arena = self

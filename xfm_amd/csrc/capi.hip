@@ -300,6 +300,11 @@ int xfm_ce_soft_bwd(const float* logits, long ld, const float* target, long ldt,
   XFM_REQUIRE(logits && target && lse && tsum && scale && dlogits, "ce_soft_bwd: null operand");
   return xfm_ce_soft_bwd_impl(logits, ld, target, ldt, R, V, lse, tsum, scale, per_row_scale, dlogits, ldd, ST(stream));
 }
+int xfm_ce_topk_eval(const float* logits, long ld, int R, int V, const int64_t* labels, int k1, int k2, float* row_loss, int* row_rank,
+                     float* acc, void* stream) {
+  XFM_REQUIRE(logits && labels && acc, "ce_topk_eval: null operand");
+  return xfm_ce_topk_eval_impl(logits, ld, R, V, labels, k1, k2, row_loss, row_rank, acc, ST(stream));
+}
 int xfm_mixup(float* x, int B, int C, int H, int W, const float* lam, const int* box, void* stream) {
   XFM_REQUIRE(x && lam && box, "mixup: null operand");
   return xfm_mixup_impl(x, B, C, H, W, lam, box, ST(stream));
@@ -331,7 +336,12 @@ int xfm_box_loss_bwd(const double* state, const float* g, int bs, float* dcoord,
 int xfm_adamw(const xfm_adamw_args* a, void* stream) {
   NOTNULL(a, "adamw");
   XFM_REQUIRE(a->p && a->g && a->m && a->v && a->group, "adamw: null operand");
-  return xfm_adamw_impl(*a, ST(stream));
+  return xfm_adamw_impl(*a, false, ST(stream));
+}
+int xfm_adamw_torch(const xfm_adamw_args* a, void* stream) {
+  NOTNULL(a, "adamw_torch");
+  XFM_REQUIRE(a->p && a->g && a->m && a->v && a->group, "adamw_torch: null operand");
+  return xfm_adamw_impl(*a, true, ST(stream));
 }
 int xfm_sumsq(const float* x, long n, float* out, float* workspace, void* stream) {
   XFM_REQUIRE(x && out && workspace, "sumsq: null operand");

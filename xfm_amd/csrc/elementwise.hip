@@ -571,6 +571,10 @@ int xfm_ce_bwd_impl(const float* logits, long ld, int R, int V, const int64_t* l
 // global-norm clip factor folded in (apex_ddp_accelerator.py:100-110).  Per-element group id selects lr / decay.
 // ---------------------------------------------------------------------------------------------
 typedef xfm_adamw_args AdamArgs;
+// TORCH = false: the transformers rule above (eps before the bias correction, decay after the update).
+// TORCH = true: torch.optim.AdamW's single-tensor rule (Imagenet.py:569-570 builds that optimizer): decay first, eps after sqrt(v) is
+// divided by sqrt(bc2).  Same traffic, same launch shape; only the arithmetic of the element differs.
+template <bool TORCH>
 __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
   const float cc = a.clip_coef ? a.clip_coef[0] : 1.f;
   for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < a.n; i += (long)gridDim.x * 1024) {
@@ -582,11 +586,18 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float gj = g[j] * cc;
-      m[j] = a.beta1 * m[j] + (1.f - a.beta1) * gj;
-      v[j] = a.beta2 * v[j] + (1.f - a.beta2) * gj * gj;
-      const float step = lr * sqrtf(a.bc2) / a.bc1;
-      p[j] -= step * m[j] / (sqrtf(v[j]) + a.eps);
-      p[j] -= lr * wd * p[j];
+      if constexpr (TORCH) {
+        p[j] *= 1.f - lr * wd;
+        m[j] = a.beta1 * m[j] + (1.f - a.beta1) * gj;
+        v[j] = a.beta2 * v[j] + (1.f - a.beta2) * gj * gj;
+        p[j] -= (lr / a.bc1) * m[j] / (sqrtf(v[j]) / sqrtf(a.bc2) + a.eps);
+      } else {
+        m[j] = a.beta1 * m[j] + (1.f - a.beta1) * gj;
+        v[j] = a.beta2 * v[j] + (1.f - a.beta2) * gj * gj;
+        const float step = lr * sqrtf(a.bc2) / a.bc1;
+        p[j] -= step * m[j] / (sqrtf(v[j]) + a.eps);
+        p[j] -= lr * wd * p[j];
+      }
     }
     *reinterpret_cast<f32x4*>(a.p + i) = p;
     *reinterpret_cast<f32x4*>(a.m + i) = m;
@@ -594,12 +605,13 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
     if (a.zero_grad) *reinterpret_cast<f32x4*>(a.g + i) = f32x4{0.f, 0.f, 0.f, 0.f};  // zero_grad() in the same sweep (Pretrain.py:76)
   }
 }
-int xfm_adamw_impl(const AdamArgs& a, hipStream_t st) {
+int xfm_adamw_impl(const AdamArgs& a, bool torch_rule, hipStream_t st) {
   XFM_REQUIRE(a.n > 0 && a.n % 256 == 0, "adamw: arena length %ld must be a positive multiple of 256", a.n);
   int grid = cdiv(a.n, 1024);
   if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, st, a);
-  return xfm_check_launch("adamw");
+  if (torch_rule) hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid), dim3(256), 0, st, a);
+  return xfm_check_launch(torch_rule ? "adamw_torch" : "adamw");
 }
 
 // out[0] += sum of squares of an fp32 vector, DETERMINISTIC: block partials in a fixed grid, then one workgroup adds them in a

@@ -192,6 +192,136 @@ int xfm_ce_soft_bwd_impl(const float* logits, long ld, const float* target, long
 }
 
 // ---------------------------------------------------------------------------------------------
+// The evaluation step of the ImageNet loop in one pass (Imagenet.py:495-536 evaluate: CrossEntropyLoss, accuracy(topk=(1, 2)) and two
+// .item() per validation batch): per row the log-sum-exp, the loss lse - x[label] and the label's RANK = its position in a stable
+// descending sort = #{j: x[j] > x[label]} + #{j < label: x[j] == x[label]}; the label is in the top k iff rank < k.  One workgroup per row,
+// online max / sum-exp as above next to the integer count; 16-byte loads when every row starts on 16 bytes (VEC), scalar loads
+// otherwise (ld is free here: num_labels of the shipped configs is 2 ... 1000, most of them no multiple of 4).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+struct TopkRow {
+  float loss;
+  int rank;
+};
+// whole workgroup (256 threads) on one row; the result is valid in thread 0.  A label outside [0, V): loss 0, rank V.
+template <bool VEC>
+__device__ __forceinline__ TopkRow ce_topk_row(const float* __restrict__ x, int V, int64_t label, float (*red)[2], int* redc) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const bool valid = label >= 0 && label < V;
+  const int lab = valid ? (int)label : 0;
+  const float xl = valid ? x[lab] : 0.f;
+  OnlineLse o;
+  int ahead = 0;
+  auto take1 = [&](const float a, int c) {
+    o.add1(a);
+    ahead += (a > xl || (a == xl && c < lab)) ? 1 : 0;
+  };
+  if (VEC) {
+    const int Vv = V & ~3;
+    for (int c = tid * 4; c < Vv; c += 1024) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(x + c);
+      o.add4(a);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ahead += (a[i] > xl || (a[i] == xl && c + i < lab)) ? 1 : 0;
+    }
+    if (tid < V - Vv) take1(x[Vv + tid], Vv + tid);   // the scalar tail: at most 3 columns
+  } else {
+    for (int c = tid; c < V; c += 256) take1(x[c], c);
+  }
+  const float wm = wave_max(o.m);
+  const float ws = wave_sum(o.s * __expf(o.m - wm));
+  ahead = wave_sum_int(ahead);
+  __syncthreads();   // (the previous row's readers of red / redc are done: the serial form calls this in a loop)
+  if (lane == 0) { red[w][0] = wm; red[w][1] = ws; redc[w] = ahead; }
+  __syncthreads();
+  TopkRow r{0.f, V};
+  if (tid == 0 && valid) {
+    const float m = fmaxf(fmaxf(red[0][0], red[1][0]), fmaxf(red[2][0], red[3][0]));
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s += red[i][1] * __expf(red[i][0] - m);
+    r.loss = (m + __logf(s)) - xl;
+    r.rank = (redc[0] + redc[1]) + (redc[2] + redc[3]);
+  }
+  return r;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ce_topk_rows_kernel(const float* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels,
+                                                           float* __restrict__ row_loss, int* __restrict__ row_rank) {
+  __shared__ float red[4][2];
+  __shared__ int redc[4];
+  const long row = blockIdx.x;
+  const TopkRow r = ce_topk_row<VEC>(logits + row * ld, V, labels[row], red, redc);
+  if (threadIdx.x == 0) { row_loss[row] = r.loss; row_rank[row] = r.rank; }
+}
+
+// the trailing workgroup: acc[0] += sum_r loss_r, acc[1] += #{rank_r < k1}, acc[2] += #{rank_r < k2}, the rows added one after the other in
+// ascending order by ONE thread (256 rows at a time through LDS): no atomics, no tree whose shape depends on R
+__global__ __launch_bounds__(256) void ce_topk_acc_kernel(const float* __restrict__ row_loss, const int* __restrict__ row_rank, int R, int k1,
+                                                          int k2, float* __restrict__ acc) {
+  __shared__ float sl[256];
+  __shared__ int sr[256];
+  float s = 0.f;
+  int c1 = 0, c2 = 0;
+  for (int base = 0; base < R; base += 256) {
+    const int r = base + threadIdx.x;
+    if (r < R) { sl[threadIdx.x] = row_loss[r]; sr[threadIdx.x] = row_rank[r]; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int n = R - base < 256 ? R - base : 256;
+      for (int i = 0; i < n; ++i) { s += sl[i]; c1 += sr[i] < k1 ? 1 : 0; c2 += sr[i] < k2 ? 1 : 0; }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { acc[0] += s; acc[1] += (float)c1; acc[2] += (float)c2; }
+}
+
+// row_loss or row_rank NULL: the library owns no scratch memory to park the rows in, so ONE workgroup walks the rows itself, in the same
+// order with the same per-row arithmetic (the sums are bit-identical to the two-kernel form); slower, meant for small R
+template <bool VEC>
+__global__ __launch_bounds__(256) void ce_topk_serial_kernel(const float* __restrict__ logits, long ld, int R, int V,
+                                                             const int64_t* __restrict__ labels, int k1, int k2, float* __restrict__ row_loss,
+                                                             int* __restrict__ row_rank, float* __restrict__ acc) {
+  __shared__ float red[4][2];
+  __shared__ int redc[4];
+  float s = 0.f;
+  int c1 = 0, c2 = 0;
+  for (long row = 0; row < R; ++row) {
+    const TopkRow r = ce_topk_row<VEC>(logits + row * ld, V, labels[row], red, redc);
+    if (threadIdx.x == 0) {
+      s += r.loss; c1 += r.rank < k1 ? 1 : 0; c2 += r.rank < k2 ? 1 : 0;
+      if (row_loss != nullptr) row_loss[row] = r.loss;
+      if (row_rank != nullptr) row_rank[row] = r.rank;
+    }
+  }
+  if (threadIdx.x == 0) { acc[0] += s; acc[1] += (float)c1; acc[2] += (float)c2; }
+}
+
+int xfm_ce_topk_eval_impl(const float* logits, long ld, int R, int V, const int64_t* labels, int k1, int k2, float* row_loss, int* row_rank,
+                          float* acc, hipStream_t st) {
+  XFM_REQUIRE(R >= 1 && k1 >= 1 && k2 >= k1 && k2 <= V && ld >= V, "ce_topk_eval: bad arguments R=%d V=%d ld=%ld k1=%d k2=%d (need R >= 1, 1 <= k1 <= k2 <= V <= ld)",
+              R, V, ld, k1, k2);
+  const bool vec = (ld & 3) == 0 && aligned16(logits);   // every row starts on 16 bytes
+  if (row_loss == nullptr || row_rank == nullptr) {
+    if (vec) hipLaunchKernelGGL(ce_topk_serial_kernel<true>, dim3(1), dim3(256), 0, st, logits, ld, R, V, labels, k1, k2, row_loss, row_rank, acc);
+    else hipLaunchKernelGGL(ce_topk_serial_kernel<false>, dim3(1), dim3(256), 0, st, logits, ld, R, V, labels, k1, k2, row_loss, row_rank, acc);
+    return xfm_check_launch("ce_topk_eval");
+  }
+  if (vec) hipLaunchKernelGGL(ce_topk_rows_kernel<true>, dim3(R), dim3(256), 0, st, logits, ld, V, labels, row_loss, row_rank);
+  else hipLaunchKernelGGL(ce_topk_rows_kernel<false>, dim3(R), dim3(256), 0, st, logits, ld, V, labels, row_loss, row_rank);
+  int rc = xfm_check_launch("ce_topk_eval");
+  if (rc != XFM_OK) return rc;
+  hipLaunchKernelGGL(ce_topk_acc_kernel, dim3(1), dim3(256), 0, st, row_loss, row_rank, R, k1, k2, acc);
+  return xfm_check_launch("ce_topk_eval_acc");
+}
+
+// ---------------------------------------------------------------------------------------------
 // timm Mixup._mix_batch / _mix_elem in place (Imagenet.py:468-469): row i against the ORIGINAL row j = B - 1 - i.  blockIdx.y = the pair
 // (i, j), i < B / 2; one lane owns VEC consecutive elements of both rows, loads both originals and writes both results, so no second
 // buffer is needed.  Per row: lam == 1 leaves it alone (timm skips it too); an empty box mixes, x_i <- lam_i x_i + (1 - lam_i) x_j; a

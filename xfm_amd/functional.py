@@ -869,6 +869,26 @@ def ce_soft_bwd(logits, V, target, lse, tsum, scale, ldd):
     return d
 
 
+def ce_topk_eval(logits, V, labels, k1, k2, acc, rows=True):
+    """The evaluation step in one pass (xfm_ce_topk_eval): logits fp32 [R, ld>=V] (any ld, any base alignment), labels int64 [R];
+    acc fp32 [3] += (sum of the rows' CE losses, #{rank < k1}, #{rank < k2}), rank = the label's position in a stable descending sort.
+    -> (row_loss fp32 [R], row_rank int32 [R]); rows=False passes NULL for both (one workgroup walks the rows) and returns None.
+    A label outside [0, V) is an argument error here when the labels are host-visible; device labels are not read back."""
+    R = _ce_rows(logits, V)
+    assert labels.dtype == torch.int64 and labels.numel() == R and labels.is_contiguous()
+    assert acc.dtype == F32 and acc.numel() >= 3 and acc.is_contiguous()
+    if not labels.is_cuda:
+        if R and (int(labels.min()) < 0 or int(labels.max()) >= V):
+            raise ValueError(f"ce_topk_eval: label outside [0, {V})")
+        labels = labels.to(logits.device)
+    _dev(acc)
+    row_loss = torch.empty(R, dtype=F32, device=logits.device) if rows else None
+    row_rank = torch.empty(R, dtype=torch.int32, device=logits.device) if rows else None
+    check(_lib.load().xfm_ce_topk_eval(logits.data_ptr(), logits.stride(0), R, V, labels.data_ptr(), int(k1), int(k2), _ptr(row_loss),
+                                       _ptr(row_rank), acc.data_ptr(), _stream()), "ce_topk_eval")
+    return (row_loss, row_rank) if rows else None
+
+
 def mixup_(x, lam, box):
     """In-place batch mix (xfm_mixup): x fp32 [B, C, H, W] contiguous, B even; row i against the original row B - 1 - i with lam fp32 [B]
     and box int32 [B, 4] = (yl, yh, xl, xh) on the device (lam 1: untouched; empty box: mixup; else CutMix inside the box) -> x."""
@@ -898,15 +918,19 @@ def sumsq(x, out):
     check(_lib.load().xfm_sumsq(x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), _stream()), "sumsq")
 
 
-def adamw(p, g, m, v, group, lrs, wds, beta1, beta2, eps, step, clip_coef=None, zero_grad=False):
-    """zero_grad: g is zeroed in the same sweep (saves the separate fill pass over the live gradient ranges)."""
+def adamw(p, g, m, v, group, lrs, wds, beta1, beta2, eps, step, clip_coef=None, zero_grad=False, rule="transformers"):
+    """zero_grad: g is zeroed in the same sweep (saves the separate fill pass over the live gradient ranges).
+    rule: "transformers" (xfm_adamw: eps before the bias correction, decay after the update) or "torch" (xfm_adamw_torch:
+    torch.optim.AdamW's order -- decay first, eps after sqrt(v) / sqrt(bc2))."""
+    assert rule in ("transformers", "torch"), rule
     a = AdamWArgs(p=p.data_ptr(), g=g.data_ptr(), m=m.data_ptr(), v=v.data_ptr(), group=group.data_ptr(),
                   beta1=beta1, beta2=beta2, eps=eps, bc1=1.0 - beta1 ** step, bc2=1.0 - beta2 ** step,
                   clip_coef=_ptr(clip_coef), n=p.numel(), zero_grad=int(zero_grad))
     for i in range(4):
         a.lr[i] = lrs[i] if i < len(lrs) else 0.0
         a.wd[i] = wds[i] if i < len(wds) else 0.0
-    check(_lib.load().xfm_adamw(ctypes.byref(a), _stream()), "adamw")
+    lib = _lib.load()
+    check((lib.xfm_adamw_torch if rule == "torch" else lib.xfm_adamw)(ctypes.byref(a), _stream()), "adamw")
 
 
 def relpos_sorted_index(index32, entries):

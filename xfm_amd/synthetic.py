@@ -260,3 +260,12 @@ def region_batch(batch_size, max_images, max_regions, seed=1234, image_res=224, 
     image = gaussian(tag + ".image", (n_img, 3, image_res, image_res), 1.0)
     return (image, torch.from_numpy(idx), b["text_ids"], b["text_atts"], b["text_ids_masked"], b["masked_pos"], b["masked_ids"],
             torch.from_numpy(atts), torch.from_numpy(target), torch.from_numpy(is_image))
+
+
+def imagenet_batch(batch_size, seed=1234, image_res=224, num_labels=1000):
+    """(images fp32 [B, 3, res, res], labels int64 [B]) in the tuple layout of Imagenet.py:453's loader: formula images (unit Gaussian, what
+    Normalize leaves) and formula labels in [0, num_labels), pure functions of (seed, index)."""
+    image = gaussian(f"imagenet.image.{seed}", (batch_size, 3, image_res, image_res))
+    u = uniform01("imagenet.label", batch_size, seed)
+    labels = torch.from_numpy(np.minimum((u * num_labels).astype(np.int64), num_labels - 1))
+    return image, labels
