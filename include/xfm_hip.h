@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 13
+#define XFM_ABI_VERSION 14
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -498,6 +498,37 @@ int xfm_ce_soft_bwd(const float* logits, long ld, const float* target, long ldt,
  * XFM_E_ARG (nothing is launched): k1 < 1, k2 < k1, k2 > V, ld < V, R < 1, or a NULL logits / labels / acc. */
 int xfm_ce_topk_eval(const float* logits, long ld, int R, int V, const int64_t* labels, int k1, int k2, float* row_loss, int* row_rank,
                      float* acc, void* stream);
+
+/* ---- Answer ranking of the VQA evaluation (VQA.py:75-100 -> model_generation.py:146-202 rank_answer; ABI 14) ---------------------------
+ * Answers are ranked, not generated: the first decoder pass gives first-token logits, xfm_answer_shortlist keeps the k most probable
+ * candidates of every question, the second decoder pass gives each shortlisted candidate's summed NLL, xfm_answer_rerank re-ranks.
+ * One workgroup per question, no atomics; both give the same bits with and without XFM_DETERMINISTIC.
+ *
+ * THE TIE RULE (both functions): several candidates share a first token, so equal probabilities are normal.  The order is by the key
+ * (probability descending, position ascending) -- EQUAL PROBABILITIES ORDER BY ASCENDING CANDIDATE INDEX (xfm_answer_rerank: by ascending
+ * position in the shortlist).  The key is unique, so the result does not depend on the launch geometry.  torch.topk leaves the order of
+ * ties unspecified; torch.sort(stable=True, descending=True) is this rule.
+ *
+ * xfm_answer_shortlist: logits fp32 [Q, ld] with V live columns (any ld >= V, any base alignment: 16-byte loads when every row starts
+ * on 16 bytes, scalar loads otherwise), first_tok int64 [A] = the first answer token of every candidate.  Per question, in fp32:
+ *   max and sum of exp over all V logits;  p[a] = exp(l[first_tok[a]] - max) / sum;  the k largest p in descending order ->
+ *   prob fp32 [Q, k], cand int64 [Q, k] (candidate indices).
+ * A first token outside [0, V) is the caller's error; such a candidate gets probability 0 (nothing is read out of bounds).
+ * The candidates are sorted in LDS, which sets the caps below.  XFM_E_ARG (nothing is launched): k < 1, k > A, k > XFM_ANSWER_MAX_K,
+ * A > XFM_ANSWER_MAX_A, Q < 1, V < 1, ld < V, or a NULL operand.
+ *
+ * xfm_answer_rerank: prob fp32 [Q, k] and cand int64 [Q, k] as above, seq_loss fp32 [Q * k] question-major = the decoder's summed NLL of
+ * every shortlisted candidate.  Per question: s = log(prob) - seq_loss (prob 0 gives -inf, as torch; a question whose scores are ALL
+ * -inf is undefined), softmax over the k, sort descending with the tie rule on the position ->
+ *   topk_probs fp32 [Q, k], topk_ids int64 [Q, k] (candidate ids in the new order), and, when result is not NULL,
+ *   result[result_offset + q] = topk_ids[q, 0]: the answers of a whole evaluation pass collect in ONE device buffer, read once.
+ * XFM_E_ARG: k < 1, k > XFM_ANSWER_MAX_K, Q < 1, result_offset < 0, or a NULL operand (result may be NULL). */
+#define XFM_ANSWER_MAX_A 8192
+#define XFM_ANSWER_MAX_K 1024
+int xfm_answer_shortlist(const float* logits, long ld, int Q, int V, const int64_t* first_tok, int A, int k, float* prob, int64_t* cand,
+                         void* stream);
+int xfm_answer_rerank(const float* prob, const float* seq_loss, const int64_t* cand, int Q, int k, int64_t* topk_ids, float* topk_probs,
+                      int64_t* result, long result_offset, void* stream);
 
 /* ---- Device Mixup / CutMix (timm Mixup._mix_batch / _mix_elem and mixup_target as called at Imagenet.py:468-469; ABI 10) -------------
  * xfm_mixup: fp32 images [B, C, H, W], B even, mixed IN PLACE: row i against the original row j = B - 1 - i, with the per-row device

@@ -3,6 +3,7 @@
 
     python3 run.py --task pretrain_DIY --dist 1 --config configs/Pretrain_synthetic.yaml --output_dir output/pt
     python3 run.py --task imagenet --dist gpu0 --config configs/Imagenet_synthetic.yaml --output_dir output/in
+    python3 run.py --task vqa --dist 1 --config configs/VQA_synthetic.yaml --output_dir output/vqa [--evaluate]
 
 `--dist` follows run.py:44-75: '1' / 'all' = every visible GPU of this node, 'f4' / 'l4' = the first / last four, 'gpuK' = GPU K
 alone.  The reference builds a `torch.distributed.launch --use_env` shell line and hands it to os.system; here the ranks are started
@@ -19,8 +20,9 @@ if ROOT not in sys.path:
 
 from xfm_amd.launch import launch, launch_command, visible_gpu_count  # noqa: E402
 
-TASK_SCRIPTS = {"pretrain_DIY": "Pretrain.py", "imagenet": "Imagenet.py"}
-DEFAULT_CONFIGS = {"pretrain_DIY": "configs/Pretrain_synthetic.yaml", "imagenet": "configs/Imagenet_synthetic.yaml"}
+TASK_SCRIPTS = {"pretrain_DIY": "Pretrain.py", "imagenet": "Imagenet.py", "vqa": "VQA.py"}
+DEFAULT_CONFIGS = {"pretrain_DIY": "configs/Pretrain_synthetic.yaml", "imagenet": "configs/Imagenet_synthetic.yaml",
+                   "vqa": "configs/VQA_synthetic.yaml"}
 
 
 def get_dist(args, n_visible=None):
@@ -49,6 +51,10 @@ def task_command(args, n_visible=None):
     nproc, vis = get_dist(args, n_visible)
     if args.task == "imagenet":   # run.py:275-287: no --bs, no --epoch
         script_args = ["--config", args.config, "--output_dir", args.output_dir, "--seed", args.seed]
+    elif args.task == "vqa":      # run.py:182-193: --bs is the global batch (VQA.py:134-135 divides it), --evaluate is passed on
+        script_args = ["--config", args.config, "--output_dir", args.output_dir, "--bs", args.bs, "--seed", args.seed]
+        if args.evaluate:
+            script_args += ["--evaluate"]
     else:
         script_args = ["--seed", args.seed, "--epoch", args.epoch, "--config", args.config, "--output_dir", args.output_dir]
         if args.bs > 0:

@@ -38,6 +38,7 @@ int xfm_cu_count() {
 #include "losses.hip"
 #include "losses_soft.hip"
 #include "region.hip"
+#include "answer_rank.hip"
 #include "dp.hip"
 
 #define ST(s) ((hipStream_t)(s))
@@ -304,6 +305,16 @@ int xfm_ce_topk_eval(const float* logits, long ld, int R, int V, const int64_t* 
                      float* acc, void* stream) {
   XFM_REQUIRE(logits && labels && acc, "ce_topk_eval: null operand");
   return xfm_ce_topk_eval_impl(logits, ld, R, V, labels, k1, k2, row_loss, row_rank, acc, ST(stream));
+}
+int xfm_answer_shortlist(const float* logits, long ld, int Q, int V, const int64_t* first_tok, int A, int k, float* prob, int64_t* cand,
+                         void* stream) {
+  XFM_REQUIRE(logits && first_tok && prob && cand, "answer_shortlist: null operand");
+  return xfm_answer_shortlist_impl(logits, ld, Q, V, first_tok, A, k, prob, cand, ST(stream));
+}
+int xfm_answer_rerank(const float* prob, const float* seq_loss, const int64_t* cand, int Q, int k, int64_t* topk_ids, float* topk_probs,
+                      int64_t* result, long result_offset, void* stream) {
+  XFM_REQUIRE(prob && seq_loss && cand && topk_ids && topk_probs, "answer_rerank: null operand");
+  return xfm_answer_rerank_impl(prob, seq_loss, cand, Q, k, topk_ids, topk_probs, result, result_offset, ST(stream));
 }
 int xfm_mixup(float* x, int B, int C, int H, int W, const float* lam, const int* box, void* stream) {
   XFM_REQUIRE(x && lam && box, "mixup: null operand");

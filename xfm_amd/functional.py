@@ -889,6 +889,48 @@ def ce_topk_eval(logits, V, labels, k1, k2, acc, rows=True):
     return (row_loss, row_rank) if rows else None
 
 
+ANSWER_MAX_A, ANSWER_MAX_K = _lib.ANSWER_MAX_A, _lib.ANSWER_MAX_K   # the caps of the two answer-ranking kernels (include/xfm_hip.h)
+
+
+def answer_rank_ok(A, k):
+    """Shapes xfm_answer_shortlist / xfm_answer_rerank cover (the candidates are sorted in LDS); a caller outside them keeps the ATen path."""
+    return 1 <= k <= min(A, ANSWER_MAX_K) and A <= ANSWER_MAX_A
+
+
+def answer_shortlist(logits, V, first_tok, k):
+    """xfm_answer_shortlist: logits fp32 [Q, ld >= V] (any ld, any base alignment), first_tok int64 [A] -> (prob fp32 [Q, k], cand int64
+    [Q, k]): the k most probable candidates per question, probability descending, equal probabilities by ascending candidate index."""
+    _dev(logits)
+    _dev(first_tok)
+    assert logits.dtype == F32 and logits.dim() == 2 and logits.stride(1) == 1
+    assert first_tok.dtype == torch.int64 and first_tok.dim() == 1 and first_tok.is_contiguous()
+    Q, A = logits.shape[0], first_tok.numel()
+    prob = torch.empty(Q, int(k), dtype=F32, device=logits.device)
+    cand = torch.empty(Q, int(k), dtype=torch.int64, device=logits.device)
+    check(_lib.load().xfm_answer_shortlist(logits.data_ptr(), logits.stride(0), Q, int(V), first_tok.data_ptr(), A, int(k), prob.data_ptr(),
+                                           cand.data_ptr(), _stream()), "answer_shortlist")
+    return prob, cand
+
+
+def answer_rerank(prob, seq_loss, cand, result=None, result_offset=0):
+    """xfm_answer_rerank: prob fp32 [Q, k], seq_loss fp32 [Q * k] (question-major), cand int64 [Q, k] -> (topk_ids int64 [Q, k], topk_probs
+    fp32 [Q, k]) = softmax(log(prob) - seq_loss) sorted descending, ties by position; result (int64 device buffer, optional):
+    result[result_offset + q] = topk_ids[q, 0]."""
+    for t in (prob, seq_loss, cand):
+        _dev(t)
+    Q, k = prob.shape
+    assert prob.dtype == F32 and prob.is_contiguous() and cand.dtype == torch.int64 and cand.is_contiguous() and cand.shape == prob.shape
+    assert seq_loss.dtype == F32 and seq_loss.numel() == Q * k and seq_loss.is_contiguous()
+    if result is not None:
+        _dev(result)
+        assert result.dtype == torch.int64 and result.is_contiguous() and 0 <= result_offset and result_offset + Q <= result.numel()
+    topk_ids = torch.empty_like(cand)
+    topk_probs = torch.empty_like(prob)
+    check(_lib.load().xfm_answer_rerank(prob.data_ptr(), seq_loss.data_ptr(), cand.data_ptr(), Q, k, topk_ids.data_ptr(), topk_probs.data_ptr(),
+                                        _ptr(result), int(result_offset), _stream()), "answer_rerank")
+    return topk_ids, topk_probs
+
+
 def mixup_(x, lam, box):
     """In-place batch mix (xfm_mixup): x fp32 [B, C, H, W] contiguous, B even; row i against the original row B - 1 - i with lam fp32 [B]
     and box int32 [B, 4] = (yl, yh, xl, xh) on the device (lam 1: untouched; empty box: mixup; else CutMix inside the box) -> x."""

@@ -9,6 +9,7 @@ from types import SimpleNamespace
 import torch
 import torch.nn.functional as F
 
+from . import functional as Fx
 from .xfm import RobertaConfig, XFMBase, load_pretrained
 from .xroberta import RobertaForCausalLM
 
@@ -85,10 +86,11 @@ class XFMForVQA(XFMBase):
         return self.get_cross_embeds(image_embeds, image_atts, text_embeds=text_embeds, text_atts=question.attention_mask,
                                      is_pretrain=False)
 
-    def forward(self, image, quesiton, answer=None, k=None, weights=None, train=True):
+    def forward(self, image, quesiton, answer=None, k=None, weights=None, train=True, fused=False, result=None, result_offset=0):
         """(the reference spells the argument `quesiton`; kept for keyword compatibility.)
         train: k[b] = number of answers of question b, weights = one weight per answer; returns the weighted loss / batch size.
-        eval: answer = the candidate answer list, k = how many to re-rank; returns (topk_ids, topk_probs)."""
+        eval: answer = the candidate answer list, k = how many to re-rank; returns (topk_ids, topk_probs).  `fused`, `result`,
+        `result_offset` (extensions, evaluation only): see rank_answer."""
         question, answer = _fields(quesiton), _fields(answer)
         question_output = self._question_states(image, question)
         if train:
@@ -104,10 +106,46 @@ class XFMForVQA(XFMBase):
             loss = weights * answer_output.loss
             return loss.sum() / image.size(0)
         question_atts = torch.ones(question_output.size()[:-1], dtype=torch.long, device=question_output.device)
-        return self.rank_answer(question_output, question_atts, answer.input_ids, answer.attention_mask, k)
+        return self.rank_answer(question_output, question_atts, answer.input_ids, answer.attention_mask, k, fused=fused, result=result,
+                                result_offset=result_offset)
 
-    def rank_answer(self, question_states, question_atts, answer_ids, answer_atts, k):
-        """model_generation.py:146-202."""
+    def rank_answer(self, question_states, question_atts, answer_ids, answer_atts, k, fused=False, result=None, result_offset=0):
+        """model_generation.py:146-202.  `fused` (extension, default False = the reference's ATen lines, call for call): the shortlist
+        and the re-rank run on xfm_answer_shortlist / xfm_answer_rerank, whose tie rule is fixed (equal probabilities by ascending
+        candidate index; torch.topk leaves it open), and the second decoder pass reads the UNTILED question states through
+        `encoder_batch_index` -- every question's K/V is projected once per layer, not k times.  `result` (with fused): an int64 device
+        buffer; result[result_offset + q] = the winning candidate id of question q (VQA.py:95-98 without its host reads).  fused=True
+        raises on CPU tensors; with k or the number of candidates above the kernels' caps it takes the ATen path."""
+        if fused:
+            if not question_states.is_cuda:
+                raise RuntimeError("rank_answer(fused=True) runs on HIP kernels: it needs GPU tensors (fused=False is the torch path)")
+            if Fx.answer_rank_ok(answer_ids.size(0), k):
+                return self._rank_answer_fused(question_states, question_atts, answer_ids, answer_atts, k, result, result_offset)
+        topk_ids, topk_probs = self._rank_answer_aten(question_states, question_atts, answer_ids, answer_atts, k)
+        if result is not None:   # (the caps' fall-back keeps the loop's one-buffer contract)
+            result[result_offset:result_offset + topk_ids.size(0)] = topk_ids.gather(1, topk_probs.argmax(dim=1, keepdim=True)).view(-1)
+        return topk_ids, topk_probs
+
+    def _rank_answer_fused(self, question_states, question_atts, answer_ids, answer_atts, k, result, result_offset):
+        num_ques = question_states.size(0)
+        start_ids = answer_ids[0, 0].repeat(num_ques, 1)  # bos token
+        start_output = self.text_decoder(start_ids, encoder_hidden_states=question_states, encoder_attention_mask=question_atts,
+                                         return_dict=True, reduction='none')
+        logits = start_output.logits[:, 0, :]   # first token's logits: a strided fp32 view, read in place
+        if logits.dtype != torch.float32:
+            logits = logits.float()
+        prob, cand = Fx.answer_shortlist(logits, logits.size(1), answer_ids[:, 1].contiguous(), k)
+        flat = cand.view(-1)                               # [num_ques * k] candidate rows, question-major
+        input_ids = answer_ids.index_select(0, flat)
+        input_atts = answer_atts.index_select(0, flat)
+        targets_ids = input_ids.masked_fill(input_ids == self.pad_token_id, -100)
+        index = torch.arange(num_ques, device=flat.device).repeat_interleave(k)   # (no tile(): the k rows of a question share its states)
+        output = self.text_decoder(input_ids, attention_mask=input_atts, encoder_hidden_states=question_states,
+                                   encoder_attention_mask=question_atts, labels=targets_ids, return_dict=True, reduction='none',
+                                   encoder_batch_index=index)
+        return Fx.answer_rerank(prob, output.loss.float().contiguous().view(-1), cand, result, result_offset)
+
+    def _rank_answer_aten(self, question_states, question_atts, answer_ids, answer_atts, k):
         num_ques = question_states.size(0)
         start_ids = answer_ids[0, 0].repeat(num_ques, 1)  # bos token
         start_output = self.text_decoder(start_ids, encoder_hidden_states=question_states, encoder_attention_mask=question_atts,

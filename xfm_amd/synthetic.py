@@ -269,3 +269,24 @@ def imagenet_batch(batch_size, seed=1234, image_res=224, num_labels=1000):
     u = uniform01("imagenet.label", batch_size, seed)
     labels = torch.from_numpy(np.minimum((u * num_labels).astype(np.int64), num_labels - 1))
     return image, labels
+
+
+def vqa_answer_list(num_answers, seed=1234, answer_len=8, shared=2, vocab=VOCAB):
+    """A synthetic candidate answer list in the layout VQA.py:87 tokenizes (`<s> ... </s>` rows, pad = 1): (ids int64 [A, answer_len],
+    atts int64 [A, answer_len], names = the list of A answer strings).  Every first answer token is shared by `shared` candidates on
+    average (first tokens are drawn from a pool of A / shared tokens), as in the real list, where "yes", "yes it is" ... start alike: the
+    first-token probabilities of the ranking then carry ties."""
+    b = pretrain_batch(num_answers, seed=seed, max_tokens=answer_len, min_len=3, vocab=vocab, with_image=False)
+    ids = b["text_ids"].clone()
+    pool = max(num_answers // max(shared, 1), 1)
+    first = (3 + np.floor(uniform01(f"vqa_answers{seed}.pool", pool) * (vocab - 1 - 3))).astype(np.int64)
+    pick = np.minimum((uniform01(f"vqa_answers{seed}.pick", num_answers) * pool).astype(np.int64), pool - 1)
+    ids[:, 1] = torch.from_numpy(first[pick])
+    return ids, b["text_atts"], [f"answer{i}" for i in range(num_answers)]
+
+
+def vqa_eval_batch(batch_size, seed=1234, image_res=480, max_tokens=40, first_question_id=0):
+    """One test batch in the tuple layout of VQA.py:89's loader, questions as token ids: (image fp32 [B, 3, res, res], (q_ids, q_atts)
+    int64 [B, max_tokens], question_id int64 [B] = first_question_id + 0 .. B - 1)."""
+    b = pretrain_batch(batch_size, seed=seed, image_res=image_res, max_tokens=max_tokens)
+    return b["image"], (b["text_ids"], b["text_atts"]), torch.arange(first_question_id, first_question_id + batch_size)

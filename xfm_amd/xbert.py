@@ -173,12 +173,14 @@ class BertLMHeadModel(OwnsArena, nn.Module):
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, head_mask=None,
                 inputs_embeds=None, encoder_hidden_states=None, encoder_attention_mask=None, labels=None, past_key_values=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, is_decoder=True,
-                reduction='mean', mode='multi_modal', return_logits=False):
+                reduction='mean', mode='multi_modal', return_logits=False, encoder_batch_index=None):
         if past_key_values is not None or use_cache:
             raise NotImplementedError("incremental decoding caches (generation) are outside the hot-path scope")
+        # `encoder_batch_index` (extension, default None = the reference's call): row b cross-attends to encoder_hidden_states[index[b]], so
+        # rows that share a source (rank_answer's k candidates per question) have its K/V projected once per layer (RobertaModel.forward)
         outputs = self.bert(input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, position_ids=position_ids,
                             head_mask=head_mask, inputs_embeds=inputs_embeds, encoder_hidden_states=encoder_hidden_states,
-                            encoder_attention_mask=encoder_attention_mask, is_decoder=is_decoder, mode=mode)
+                            encoder_attention_mask=encoder_attention_mask, is_decoder=is_decoder, mode=mode, encoder_batch_index=encoder_batch_index)
         seq = outputs.last_hidden_state
         head = self.cls.predictions
         V = self.config.vocab_size
