@@ -10,7 +10,6 @@ a random-init checkpoint written next to the outputs (the model always loads its
 import argparse
 import json
 import os
-import random
 import sys
 import time
 
@@ -18,10 +17,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
-import yaml  # noqa: E402
+
+from xfm_amd import task as T  # noqa: E402
 
 # Imagenet.py:84-106
 DATASET2NLABELS = {'imagenet': 1000, 'food101': 101, 'cifar10': 10, 'cifar100': 100, 'stanfordcars': 196, 'fgvcaircraft': 102, 'dtd': 47,
@@ -29,21 +28,13 @@ DATASET2NLABELS = {'imagenet': 1000, 'food101': 101, 'cifar10': 10, 'cifar100': 
                    'gtsrb': 43, 'country211': 211, 'fer2013': 7, 'pcam': 2, 'kitti': 9, 'renderedsst2': 2}
 
 
-class SyntheticLoader:
+class SyntheticLoader(T.CycledBatches):
     """`steps` batches of (images, labels) in the layout of Imagenet.py:453's loader, from a small pool of distinct formula batches."""
 
     def __init__(self, steps, batch_size, seed, image_res=224, num_labels=1000, pool=4):
         from xfm_amd import synthetic as syn
-        self.steps = steps
-        self.batches = [syn.imagenet_batch(batch_size, seed=seed + 7919 * k, image_res=image_res, num_labels=num_labels)
-                        for k in range(min(pool, steps))]
-
-    def __len__(self):
-        return self.steps
-
-    def __iter__(self):
-        for i in range(self.steps):
-            yield self.batches[i % len(self.batches)]
+        super().__init__(steps, [syn.imagenet_batch(batch_size, seed=s, image_res=image_res, num_labels=num_labels)
+                                 for s in T.pool_seeds(seed, steps, pool)])
 
 
 def synthetic_loaders(config, seed, world_size=1):
@@ -73,25 +64,11 @@ def random_vision_checkpoint(config, out_dir):
 
 def main(args, config):
     from xfm_amd import imagenet_loop as IL
-    from xfm_amd.accelerators import ACCELERATOR_MAP
     from xfm_amd.model_classification import XFMForClassification
-    from xfm_amd.pretrain_loop import AttrDict
 
-    rank = int(os.environ.get("RANK", 0))
-    local_rank = int(os.environ.get("LOCAL_RANK", 0))
-    world_size = int(os.environ.get("WORLD_SIZE", 1))
-    if not torch.cuda.is_available():
-        raise RuntimeError("Imagenet.py needs a GPU: the HIP path has no CPU fallback")
-    torch.cuda.set_device(local_rank)
-    device = torch.device("cuda", local_rank)
-    if world_size > 1 and not dist.is_initialized():  # utils.init_distributed_mode
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("nccl", world_size=world_size, rank=rank)
-
+    rank, local_rank, world_size, device = T.start_process("Imagenet.py")
     seed = args.seed + rank  # Imagenet.py:544
-    torch.manual_seed(seed)
-    np.random.seed(seed)
-    random.seed(seed)
+    T.seed_all(seed)
     if not config.get("synthetic", False) or "num_labels" not in config:
         config["num_labels"] = DATASET2NLABELS[config["task_name"]]  # Imagenet.py:550 (a synthetic config may name a smaller label set)
     train_loader, val_loader = synthetic_loaders(config, seed, world_size)
@@ -110,9 +87,7 @@ def main(args, config):
     print("config['optimizer']", config["optimizer"], flush=True)
     optimizer = IL.create_optimizer(config, model)
     # the reference's loop clips nothing (no clip call between backward and step, Imagenet.py:483-485)
-    arg_acc = AttrDict(config.get("accelerator") or {"ACCELERATOR": "RCCLDDP", "RNG_SEED": seed, "GRAD_ACCUMULATE_STEPS": 1,
-                                                      "CLIP_GRAD_NORM": 0.0})
-    accelerator = ACCELERATOR_MAP[arg_acc["ACCELERATOR"]](arg_acc, logger=None)
+    accelerator = T.make_accelerator(config.get("accelerator"), seed)
     model, optimizer, _ = accelerator.set_up(model, optimizer, None, local_rank, world_size, rank)
 
     mixup_fn = IL.create_mixup(config)
@@ -138,9 +113,7 @@ def main(args, config):
             with open(os.path.join(args.output_dir, "log.txt"), "a") as f:
                 f.write("best epoch: %d" % best_epoch)   # Imagenet.py:643-645
             print("Training time {:.1f} s, best_acc1 {:.3f}".format(time.time() - start_time, best_acc1), flush=True)
-    if world_size > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    T.finish_process(world_size)
 
 
 if __name__ == "__main__":
@@ -152,9 +125,7 @@ if __name__ == "__main__":
     parser.add_argument("--device", default="cuda")
     parser.add_argument("--seed", default=42, type=int)
     a = parser.parse_args()
-    with open(a.config) as f:
-        cfg = yaml.safe_load(f)
+    cfg = T.load_yaml(a.config)
     os.makedirs(a.output_dir, exist_ok=True)
-    with open(os.path.join(a.output_dir, "config.yaml"), "w") as f:
-        yaml.safe_dump(cfg, f)
+    T.dump_yaml(cfg, a.output_dir)
     main(a, cfg)

@@ -9,7 +9,6 @@ import argparse
 import json
 import math
 import os
-import random
 import sys
 import time
 
@@ -17,86 +16,45 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
-import yaml  # noqa: E402
+
+from xfm_amd import task as T  # noqa: E402
 
 
-class SyntheticLoader:
+class SyntheticLoader(T.CycledBatches):
     """`steps` batches in the tuple layout of dataset/pretrain_dataset.py:264-312's collate: (image, text_ids, text_atts,
     text_ids_masked, masked_pos, masked_ids) -- or without the image for the text source."""
 
     def __init__(self, steps, batch_size, seed, image_res=224, max_tokens=30, max_masks=15, with_image=True, vocab=None, pool=4):
         from xfm_amd import synthetic as syn
         kw = {} if vocab is None else {"vocab": vocab}
-        self.steps = steps
-        self.batches = []
-        for k in range(min(pool, steps)):  # a small pool of distinct batches, cycled (host generation is not what is being run)
-            b = syn.pretrain_batch(batch_size, seed=seed + 7919 * k, image_res=image_res, max_tokens=max_tokens, max_masks=max_masks,
+        batches = []
+        for s in T.pool_seeds(seed, steps, pool):
+            b = syn.pretrain_batch(batch_size, seed=s, image_res=image_res, max_tokens=max_tokens, max_masks=max_masks,
                                    with_image=with_image, **kw)
             t = (b["text_ids"], b["text_atts"], b["text_ids_masked"], b["masked_pos"], b["masked_ids"])
-            self.batches.append(((b["image"],) + t) if with_image else t)
-
-    def __len__(self):
-        return self.steps
-
-    def __iter__(self):
-        for i in range(self.steps):
-            yield self.batches[i % len(self.batches)]
+            batches.append(((b["image"],) + t) if with_image else t)
+        super().__init__(steps, batches)
 
 
-class SyntheticRegionLoader:
+class SyntheticRegionLoader(T.CycledBatches):
     """`steps` region batches in the tuple layout run_region_iter unpacks (xfm_amd.synthetic.region_batch), sized by the config's
     `regions:` section (batch_size, max_images, max_regions)."""
 
     def __init__(self, steps, regions, seed, image_res=224, patch_size=16, max_tokens=30, max_masks=15, vocab=None, pool=4):
         from xfm_amd import synthetic as syn
         kw = {} if vocab is None else {"vocab": vocab}
-        self.steps = steps
-        self.batches = [syn.region_batch(regions["batch_size"], regions["max_images"], regions["max_regions"], seed=seed + 7919 * k,
-                                         image_res=image_res, patch_size=patch_size, max_tokens=max_tokens, max_masks=max_masks, **kw)
-                        for k in range(min(pool, steps))]
-
-    def __len__(self):
-        return self.steps
-
-    def __iter__(self):
-        for i in range(self.steps):
-            yield self.batches[i % len(self.batches)]
-
-
-class Checkpointer:
-    """utils/checkpointer.py:20-47, local paths only."""
-
-    def __init__(self, serialization_dir=".output"):
-        self._dir = serialization_dir
-        os.makedirs(self._dir, exist_ok=True)
-
-    def save_checkpoint(self, epoch, model_state, training_states, step=-1):
-        if step > 0:
-            torch.save(model_state, os.path.join(self._dir, "model_state_step_{}.th".format(step)))
-        else:
-            torch.save(model_state, os.path.join(self._dir, "model_state_epoch_{}.th".format(epoch)))
-            torch.save({**training_states, "epoch": epoch}, os.path.join(self._dir, "training_state_latest.th"))
+        super().__init__(steps, [syn.region_batch(regions["batch_size"], regions["max_images"], regions["max_regions"], seed=s,
+                                                  image_res=image_res, patch_size=patch_size, max_tokens=max_tokens, max_masks=max_masks,
+                                                  **kw) for s in T.pool_seeds(seed, steps, pool)])
 
 
 def main(args, config):
     from xfm_amd import pretrain_loop as PL
-    from xfm_amd.accelerators import ACCELERATOR_MAP
     from xfm_amd.model_pretrain import XFM
 
-    rank = int(os.environ.get("RANK", 0))
-    local_rank = int(os.environ.get("LOCAL_RANK", 0))
-    world_size = int(os.environ.get("WORLD_SIZE", 1))
-    if not torch.cuda.is_available():
-        raise RuntimeError("Pretrain.py needs a GPU: the HIP path has no CPU fallback")
-    torch.cuda.set_device(local_rank)
-    device = torch.device("cuda", local_rank)
-    if world_size > 1 and not dist.is_initialized():  # utils.init_distributed_mode (utils/__init__.py:388-410)
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("nccl", world_size=world_size, rank=rank)
-
+    rank, local_rank, world_size, device = T.start_process("Pretrain.py")
     config["batch_size"] = config["images"]["batch_size"]
     if args.bs > 0:
         config["batch_size"] = config["images"]["batch_size"] = args.bs
@@ -104,9 +62,7 @@ def main(args, config):
         config["schedular"]["epochs"] = args.epoch
         print(f"### set epochs to: {args.epoch}", flush=True)
     seed = args.seed + rank  # Pretrain.py:333
-    torch.manual_seed(seed)
-    np.random.seed(seed)
-    random.seed(seed)
+    T.seed_all(seed)
 
     if config.get("train_file") and not config.get("synthetic", False):
         raise NotImplementedError("file-backed datasets (dataset/pretrain_dataset.py) are outside the hot-path scope: set "
@@ -129,13 +85,12 @@ def main(args, config):
 
     print("Creating model XFM", flush=True)
     model = XFM(config=config).to(device)
-    arg_opt = PL.AttrDict(config["optimizer"])
+    arg_opt = T.AttrDict(config["optimizer"])
     optimizer = PL.create_optimizer(arg_opt, model)
-    arg_sche = PL.AttrDict(config["schedular"])
+    arg_sche = T.AttrDict(config["schedular"])
     arg_sche["step_per_epoch"] = step_per_epoch
     lr_scheduler = PL.create_scheduler(arg_sche, optimizer)
-    arg_acc = PL.AttrDict(config["accelerator"])
-    accelerator = ACCELERATOR_MAP[arg_acc["ACCELERATOR"]](arg_acc, logger=None)
+    accelerator = T.make_accelerator(config["accelerator"], seed)
 
     start_epoch = 0
     if config.get("resume", False):  # Pretrain.py:437-441
@@ -143,7 +98,7 @@ def main(args, config):
     if args.checkpoint and os.path.exists(args.checkpoint):
         model.load_pretrained(args.checkpoint, config, is_domain_pretrain=True)
     model, optimizer, lr_scheduler = accelerator.set_up(model, optimizer, lr_scheduler, local_rank, world_size, rank)
-    checkpointer = Checkpointer(args.output_dir)
+    checkpointer = T.Checkpointer(args.output_dir)
     print("### output_dir, ", args.output_dir, flush=True)
 
     def log(step, avg):
@@ -161,11 +116,9 @@ def main(args, config):
     if rank == 0:
         with open(os.path.join(args.output_dir, "log.txt"), "a") as f:
             f.write(json.dumps({**{f"train_{k}": v for k, v in stats.items()}, "epochs": config["schedular"]["epochs"]}) + "\n")
-        with open(os.path.join(args.output_dir, "config.yaml"), "w") as f:
-            yaml.safe_dump(config, f)
+        T.dump_yaml(config, args.output_dir)
         print("### Time {:.1f} s".format(time.time() - start_time), flush=True)
-    if world_size > 1:
-        dist.destroy_process_group()
+    T.finish_process(world_size, barrier=False)
 
 
 if __name__ == "__main__":
@@ -179,7 +132,6 @@ if __name__ == "__main__":
     parser.add_argument("--bs", default=-1, type=int)
     parser.add_argument("--distributed", action="store_false")
     a = parser.parse_args()
-    with open(a.config) as f:
-        cfg = yaml.safe_load(f)
+    cfg = T.load_yaml(a.config)
     os.makedirs(a.output_dir, exist_ok=True)
     main(a, cfg)

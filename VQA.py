@@ -11,7 +11,6 @@ its random initialisation.
 import argparse
 import math
 import os
-import random
 import sys
 import time
 
@@ -19,33 +18,23 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
-import torch.distributed as dist  # noqa: E402
-import yaml  # noqa: E402
 
-from Pretrain import Checkpointer  # noqa: E402
+from xfm_amd import task as T  # noqa: E402
 
 
-class SyntheticTrainLoader:
+class SyntheticTrainLoader(T.CycledBatches):
     """`steps` batches (image, question, answer, weights, n) in the layout of VQA.py:46's loader with token ids for strings, from a small
     pool of distinct formula batches."""
 
     def __init__(self, steps, batch_size, seed, image_res=480, max_tokens=40, max_answers=10, answer_len=8, pool=4):
         from xfm_amd import synthetic as syn
-        self.steps = steps
-        self.batches = []
-        for k in range(min(pool, steps)):
-            x = syn.vqa_batch(batch_size, seed=seed + 7919 * k, image_res=image_res, max_tokens=max_tokens, max_answers=max_answers,
+        batches = []
+        for s in T.pool_seeds(seed, steps, pool):
+            x = syn.vqa_batch(batch_size, seed=s, image_res=image_res, max_tokens=max_tokens, max_answers=max_answers,
                               answer_len=answer_len)
-            self.batches.append((x.image, (x.q_ids, x.q_atts), (x.a_ids, x.a_atts), x.weights, x.k))
-
-    def __len__(self):
-        return self.steps
-
-    def __iter__(self):
-        for i in range(self.steps):
-            yield self.batches[i % len(self.batches)]
+            batches.append((x.image, (x.q_ids, x.q_atts), (x.a_ids, x.a_atts), x.weights, x.k))
+        super().__init__(steps, batches)
 
 
 class SyntheticTestSet:
@@ -59,21 +48,17 @@ class SyntheticTestSet:
         self.ann = [{"question_id": q} for q in range(num_questions)]
 
 
-class SyntheticTestLoader:
+class SyntheticTestLoader(T.CycledBatches):
     """`steps` batches (image, question, question_id) in the layout of VQA.py:89's loader; question ids count up over the pass."""
 
     def __init__(self, steps, batch_size, seed, dataset, image_res=480, max_tokens=40, pool=2):
         from xfm_amd import synthetic as syn
-        self.steps, self.batch_size, self.dataset = steps, batch_size, dataset
-        self.batches = [syn.vqa_eval_batch(batch_size, seed=seed + 7919 * k, image_res=image_res, max_tokens=max_tokens)
-                        for k in range(min(pool, steps))]
-
-    def __len__(self):
-        return self.steps
+        super().__init__(steps, [syn.vqa_eval_batch(batch_size, seed=s, image_res=image_res, max_tokens=max_tokens)
+                                 for s in T.pool_seeds(seed, steps, pool)])
+        self.batch_size, self.dataset = batch_size, dataset
 
     def __iter__(self):
-        for i in range(self.steps):
-            image, question, qid = self.batches[i % len(self.batches)]
+        for i, (image, question, qid) in enumerate(super().__iter__()):
             yield image, question, qid + i * self.batch_size
 
 
@@ -95,26 +80,14 @@ def synthetic_loaders(config, seed, world_size=1):
 def main(args, config):
     from xfm_amd import pretrain_loop as PL
     from xfm_amd import vqa_loop as VL
-    from xfm_amd.accelerators import ACCELERATOR_MAP
     from xfm_amd.model_generation import XFMForVQA
 
-    rank = int(os.environ.get("RANK", 0))
-    local_rank = int(os.environ.get("LOCAL_RANK", 0))
-    world_size = int(os.environ.get("WORLD_SIZE", 1))
-    if not torch.cuda.is_available():
-        raise RuntimeError("VQA.py needs a GPU: the HIP path has no CPU fallback")
-    torch.cuda.set_device(local_rank)
-    device = torch.device("cuda", local_rank)
-    if world_size > 1 and not dist.is_initialized():  # utils.init_distributed_mode
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("nccl", world_size=world_size, rank=rank)
+    rank, local_rank, world_size, device = T.start_process("VQA.py")
     if args.bs > 0:
         config['batch_size_train'] = args.bs // world_size   # VQA.py:134-135
 
     seed = args.seed + rank  # VQA.py:137
-    torch.manual_seed(seed)
-    np.random.seed(seed)
-    random.seed(seed)
+    T.seed_all(seed)
     train_loader, test_loader = synthetic_loaders(config, seed, world_size)
 
     print("Creating model", flush=True)
@@ -125,15 +98,13 @@ def main(args, config):
     model = model.to(device)
     print("### Total Params: ", sum(p.numel() for p in model.parameters() if p.requires_grad), flush=True)
 
-    arg_opt = PL.AttrDict(config['optimizer'])
+    arg_opt = T.AttrDict(config['optimizer'])
     optimizer = PL.create_optimizer(arg_opt, model)
-    arg_sche = PL.AttrDict(config['schedular'])
+    arg_sche = T.AttrDict(config['schedular'])
     arg_sche['step_per_epoch'] = len(train_loader)
     lr_scheduler = PL.create_scheduler(arg_sche, optimizer)
     # the reference's loop clips nothing (no clip call between backward and step, VQA.py:56-60)
-    arg_acc = PL.AttrDict(config.get("accelerator") or {"ACCELERATOR": "RCCLDDP", "RNG_SEED": seed, "GRAD_ACCUMULATE_STEPS": 1,
-                                                       "CLIP_GRAD_NORM": 0.0})
-    accelerator = ACCELERATOR_MAP[arg_acc["ACCELERATOR"]](arg_acc, logger=None)
+    accelerator = T.make_accelerator(config.get("accelerator"), seed)
     model, optimizer, lr_scheduler = accelerator.set_up(model, optimizer, lr_scheduler, local_rank, world_size, rank)
 
     start_time = time.time()
@@ -150,7 +121,7 @@ def main(args, config):
         if rank == 0:
             print(f"### data {config['train_dataset_size']}, batch size, {config['batch_size_train']} x {world_size} x "
                   f"{config.get('accumulate_steps', 1)}", flush=True)
-        checkpointer = Checkpointer(args.output_dir)
+        checkpointer = T.Checkpointer(args.output_dir)
         results = VL.train(model, train_loader, test_loader, optimizer, device, lr_scheduler, config, accelerator, checkpointer,
                            args.output_dir, args.result_dir, print_freq=config.get("print_freq", 50))
         torch.cuda.synchronize()
@@ -159,9 +130,7 @@ def main(args, config):
                 print(f.read(), end="", flush=True)
             print("### result files, ", results, flush=True)
     print('### Time {:.1f} s'.format(time.time() - start_time), flush=True)
-    if world_size > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    T.finish_process(world_size)
 
 
 if __name__ == "__main__":
@@ -175,11 +144,9 @@ if __name__ == "__main__":
     parser.add_argument("--evaluate", action="store_true")
     parser.add_argument("--load_vqa_pretrain", action="store_true")
     a = parser.parse_args()
-    with open(a.config) as f:
-        cfg = yaml.safe_load(f)
+    cfg = T.load_yaml(a.config)
     a.result_dir = os.path.join(a.output_dir, "result")
     os.makedirs(a.output_dir, exist_ok=True)
     os.makedirs(a.result_dir, exist_ok=True)
-    with open(os.path.join(a.output_dir, "config.yaml"), "w") as f:
-        yaml.safe_dump(cfg, f)
+    T.dump_yaml(cfg, a.output_dir)
     main(a, cfg)

@@ -420,3 +420,44 @@ def test_evaluate_reads_the_device_once(gold, monkeypatch):
     assert abs(res.loss_avg - loss_sum / 6) <= 1e-5 * abs(loss_sum / 6)
     a1, a2 = IL.accuracy(torch.cat(seen).float(), target.cuda(), topk=(1, 2))   # the kernel path of accuracy(): percent, one element each
     assert a1.shape == (1,) and float(a1) == pytest.approx(res.acc1) and float(a2) == pytest.approx(res.acc2)
+
+
+# ------------------------------------------------------------------------------------------------------------- script
+@pytest.mark.parametrize("is_lp", [False, True])
+def test_imagenet_script_main_trains_saves_the_best_checkpoint_and_evaluates(gold, is_lp, tmp_path, capsys):
+    """Imagenet.py's main() as `run.py --task imagenet` starts it, at the fixture's shallow shape with synthetic loaders and no
+    `vision_config` (a random-init tower written next to the outputs): one epoch of two iterations, the validation pass,
+    checkpoint_best.pth and log.txt; then the `--evaluate` form on a fresh model."""
+    from types import SimpleNamespace as NS
+
+    import Imagenet as script
+    from xfm_amd import synthetic as syn
+    meta = gold[1]
+
+    def config():
+        cfg = loop_config(meta, is_lp, synthetic=True, batch_size_train=4, batch_size_test=8, train_dataset_size=8, val_dataset_size=32,
+                          print_freq=1, text_num_hidden_layers=0, text_fusion_start_at=0, fusion_num_hidden_layers=0,
+                          text_config={"vocab_size": 2048})
+        cfg["schedular"]["epochs"] = 1
+        return cfg
+
+    # the reference saves when acc1 > best_acc1 with best_acc1 = 0 (Imagenet.py:614-625): take the first seed whose validation labels cover
+    # every class, so that even a constant prediction scores (tests/test_imagenet_loop_host.py does the same)
+    seed = next(s for s in range(42, 400) if len({int(v) for k in range(4) for v in
+                                                  syn.imagenet_batch(8, seed=s + 104729 + 7919 * k, image_res=16, num_labels=meta["num_labels"])[1]})
+                == meta["num_labels"])
+    out = tmp_path / "imagenet"
+    out.mkdir()
+    args = NS(checkpoint="", seed=seed, evaluate=False, output_dir=str(out))
+    script.main(args, config())
+    capsys.readouterr()
+    ckpt = torch.load(out / "checkpoint_best.pth", weights_only=False)
+    assert sorted(ckpt) == ["config", "epoch", "model", "optimizer"]
+    assert ckpt["optimizer"]["param_groups"][0]["adamw_rule"] == "torch" and bool(ckpt["config"]["is_lp"]) == is_lp
+    assert (out / "log.txt").read_text().endswith("best epoch: %d" % ckpt["epoch"])
+    args.evaluate = True
+    script.main(args, config())
+    records = [json.loads(l) for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(records) == 1 and sorted(records[0]) == ["acc1", "acc2", "loss"]
+    assert all(np.isfinite(records[0][k]) for k in ("acc1", "acc2", "loss")), records
+    assert 0.0 <= records[0]["acc1"] <= records[0]["acc2"] <= 100.0

@@ -309,3 +309,53 @@ def test_train_iteration_with_a_synthetic_region_loader():
     for k in ("loss_ritc", "loss_ritm", "loss_rmlm", "loss_rbbox", "loss_rgiou", "loss_itc", "loss_mlm"):
         assert k in out and math.isfinite(float(out[k])), (k, out)
     assert float(out["loss_rbbox"]) > 0 and float(out["loss_rgiou"]) > 0
+
+
+def test_pretrain_script_main_trains_checkpoints_and_resumes(tmp_path, capsys):
+    """Pretrain.py's main() as `run.py --task pretrain` starts it, at the one-layer shape above with all three synthetic sources (text,
+    region, image): one epoch of two steps, the epoch checkpoint, log.txt and config.yaml; then a second main() that resumes from that
+    checkpoint with `epochs: 2` and trains exactly the remaining epoch."""
+    import copy
+    import os
+    from types import SimpleNamespace as NS
+
+    import yaml
+
+    import Pretrain as script
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "configs", "Pretrain_synthetic_regions.yaml")) as f:
+        shipped = yaml.safe_load(f)
+    cfg = {"use_beit_v2": True, "image_res": 224, "patch_size": 16, "local_attn_depth": -1, "text_encoder": "roberta-base",
+           "text_num_hidden_layers": 1, "text_fusion_start_at": 1, "fusion_num_hidden_layers": 1, "fusion_fusion_start_at": 0,
+           "embed_dim": 256, "temp": 0.07, "vision_depth": 1, "text_config": {"vocab_size": 2048},
+           "images": {"batch_size": 4}, "train_dataset_size": 8, "synthetic": True, "synthetic_text_source": True,
+           "regions": {"batch_size": 6, "max_images": 4, "max_regions": 2}, "ret_bbox_loss": True, "ret_bbox_giou": True,
+           "calc_image_bbox_loss": False, "ckpt_frequent": 1, "ckpt_frequent_step": 10 ** 9, "print_freq": 1,
+           "optimizer": dict(shipped["optimizer"]), "schedular": dict(shipped["schedular"], epochs=1),
+           "accelerator": dict(shipped["accelerator"])}
+    out = tmp_path / "pretrain"
+    out.mkdir()
+    args = NS(checkpoint="", bs=-1, epoch=-1, seed=42, output_dir=str(out))
+    script.main(args, copy.deepcopy(cfg))
+    steps = [json.loads(l)["step"] for l in capsys.readouterr().out.splitlines() if l.startswith('{"step"')]
+    assert steps == [1, 2]
+    assert (out / "model_state_epoch_0.th").exists() and (out / "training_state_latest.th").exists()
+    assert yaml.safe_load((out / "config.yaml").read_text())["batch_size"] == 4
+    lines = (out / "log.txt").read_text().splitlines()
+    assert len(lines) == 1
+    stats = json.loads(lines[0])
+    for k in ("train_loss_tmlm", "train_loss_ritc", "train_loss_rbbox", "train_loss_itc", "train_loss_mlm"):
+        assert math.isfinite(float(stats[k])), (k, stats)
+    assert stats["epochs"] == 1
+    # resume: the optimizer, the schedule and the epoch counter from the epoch checkpoint, the weights through load_pretrained
+    args.checkpoint = str(out / "model_state_epoch_0.th")
+    again = copy.deepcopy(cfg)
+    again["resume"] = True
+    again["schedular"]["epochs"] = 2
+    script.main(args, again)
+    steps = [json.loads(l)["step"] for l in capsys.readouterr().out.splitlines() if l.startswith('{"step"')]
+    assert steps == [3, 4]   # the remaining epoch and nothing else
+    assert (out / "model_state_epoch_1.th").exists()
+    assert torch.load(out / "training_state_latest.th", weights_only=False)["epoch"] == 1
+    lines = (out / "log.txt").read_text().splitlines()
+    assert len(lines) == 2 and json.loads(lines[1])["epochs"] == 2

@@ -10,7 +10,7 @@ Mirrors (names, argument meaning, ordering):
   * create_mixup / create_criterion   Imagenet.py:592-611
   * train                    Imagenet.py:614-637
 What differs, on purpose: the reference reads the loss with `.item()` after every training step (:477) and the loss and two accuracies
-after every validation batch (:521-523).  Here the training losses are parked (pretrain_loop.LossMeters) and read when a log line is
+after every validation batch (:521-523).  Here the training losses are parked (task.LossMeters) and read when a log line is
 due, and the evaluation adds its three sums on the device (xfm_ce_topk_eval) into one buffer that is read ONCE at the end."""
 import math
 import os
@@ -18,7 +18,8 @@ import os
 import torch
 
 from . import functional as Fx
-from .pretrain_loop import LossMeters
+from .task import LossMeters, is_distributed, is_main_process, to_device, unwrap
+from .task import read as _read  # the loop's single device-to-host read (evaluate calls it once per pass; the tests count its calls)
 
 F32 = torch.float32
 
@@ -39,11 +40,6 @@ def adjust_learning_rate(optimizer, epoch, config):
         else:
             param_group["lr"] = lr
     return lr
-
-
-def _read(t):
-    """The loop's single device-to-host read helper (evaluate calls it once per pass; the tests count its calls)."""
-    return t.tolist()
 
 
 def _topk_sums(output, target, k1, k2, acc):
@@ -131,10 +127,10 @@ def train_one_epoch(model, loader, optimizer, criterion, epoch, mixup_fn, device
     n = len(loader)
     for i, (images, target) in enumerate(loader):
         adjust_learning_rate(optimizer, i / n + epoch, config)   # FROM MAE: a per-iteration (not per-epoch) schedule (:457-458)
-        images = images.to(device, non_blocking=True)
+        images = to_device(device, images)
         if config.get('task_name') == 'kitti':
             target = target['type']
-        target = target.to(device, non_blocking=True)
+        target = to_device(device, target)
         if mixup_fn is not None:
             images, target = mixup_fn(images, target)
         output = model(images, None, None, None, False)
@@ -166,8 +162,7 @@ def evaluate(model, loader, device, log=None):
     acc = None
     count = 0
     for images, target in loader:
-        images = images.to(device, non_blocking=True)
-        target = target.to(device, non_blocking=True)
+        images, target = to_device(device, (images, target))
         output = model(images, None, None, None, False)
         if acc is None:
             acc = torch.zeros(3, dtype=F32, device=output.device)
@@ -188,9 +183,7 @@ def train(model, train_loader, val_loader, optimizer, criterion, mixup_fn, devic
     """Imagenet.py:614-637: per epoch -- train, evaluate, and on rank 0 save checkpoint_best.pth (model / optimizer / config / epoch) when
     the accuracy improved.  optimizer.state_dict() carries the fused AdamW moments in torch's own format
     (RCCLDDPAccelerator._publish_optimizer_state).  Returns (best_acc1, best_epoch)."""
-    distributed = torch.distributed.is_available() and torch.distributed.is_initialized()
-    main_process = not distributed or torch.distributed.get_rank() == 0
-    base = model.module if hasattr(model, 'module') else model
+    base = unwrap(model)
     best_acc1, best_epoch = 0, 0
     for epoch in range(0, config['schedular']['epochs']):
         if train_sampler is not None:
@@ -198,7 +191,7 @@ def train(model, train_loader, val_loader, optimizer, criterion, mixup_fn, devic
         train_one_epoch(model, train_loader, optimizer, criterion, epoch, mixup_fn, device, config, accelerator, print_freq=print_freq,
                         log=log)
         acc1 = evaluate(model, val_loader, device)
-        if main_process:
+        if is_main_process():
             is_best = acc1 > best_acc1
             best_acc1 = max(float(acc1), best_acc1)
             if is_best:
@@ -206,6 +199,6 @@ def train(model, train_loader, val_loader, optimizer, criterion, mixup_fn, devic
                 save_obj = {'model': base.state_dict(), 'optimizer': optimizer.state_dict(), 'config': config, 'epoch': epoch}
                 torch.save(save_obj, os.path.join(output_dir, 'checkpoint_best.pth'))
                 print("best_acc1 = ", best_acc1, flush=True)
-        if distributed:
+        if is_distributed():
             torch.distributed.barrier()
     return best_acc1, best_epoch

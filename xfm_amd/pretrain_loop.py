@@ -8,23 +8,10 @@ What differs, on purpose: the reference reads every loss with `.item()` right af
 step, Pretrain.py:79-91); here the loss tensors are queued and only read when a log line is due (`LossMeters.flush`), so the host
 keeps enqueueing the next step while the GPU runs."""
 import math
-from collections import OrderedDict
 
 import torch
 
-
-class AttrDict(dict):
-    """utils.AttrDict: the reference's configs are dicts read both as args['k'] and args.k."""
-
-    def __getattr__(self, k):
-        try:
-            return self[k]
-        except KeyError:
-            raise AttributeError(k)
-
-    def __setattr__(self, k, v):
-        self[k] = v
-
+from .task import AttrDict, LossMeters, is_main_process, to_device, unwrap  # noqa: F401  (AttrDict, LossMeters: re-exported)
 
 NO_DECAY = ("bias", "LayerNorm.bias", "LayerNorm.weight", "norm.bias", "norm.weight", "norm1.bias", "norm1.weight", "norm2.bias",
             "norm2.weight")  # optim.py:16-24 (substring match)
@@ -77,35 +64,8 @@ def create_scheduler(args, optimizer):
     return torch.optim.lr_scheduler.LambdaLR(optimizer, lambda s: linear_schedule(s, nw, nt), last_epoch=-1)
 
 
-class LossMeters:
-    """Running means of the per-source losses without a device sync per update: tensors are parked and read in one go."""
-
-    def __init__(self):
-        self.pending = []
-        self.total = OrderedDict()
-        self.count = OrderedDict()
-
-    def update(self, **kw):
-        for k, v in kw.items():
-            self.pending.append((k, v.detach() if torch.is_tensor(v) else v))
-
-    def flush(self):
-        for k, v in self.pending:
-            self.total[k] = self.total.get(k, 0.0) + float(v)
-            self.count[k] = self.count.get(k, 0) + 1
-        self.pending = []
-
-    def global_avg(self):
-        self.flush()
-        return {k: self.total[k] / self.count[k] for k in self.total}
-
-
 _METER_NAMES = {'image': ('loss_itc', 'loss_itm', 'loss_mlm', 'loss_mim'), 'web': ('loss_witc', 'loss_witm', 'loss_wmlm', 'loss_wmim'),
                 'imagenet': (None, None, None, 'loss_imim'), 'aux': (None, None, 'loss_amlm', None)}
-
-
-def _to(device, t):
-    return None if t is None else t.to(device, non_blocking=True)
 
 
 def _backward(accelerator, loss, optimizer, last):
@@ -120,15 +80,14 @@ def _backward(accelerator, loss, optimizer, last):
 def run_image_iter(model, image_batch, optimizer, accelerator, metric_logger, device, data_source, ret_mim_loss=True,
                    ret_match_loss=True, ret_mlm_loss=True, ret_itc_loss=True, do_optm=False):
     """Pretrain.py:61-91."""
-    image = _to(device, image_batch[0])
+    image = to_device(device, image_batch[0])
     extra = {}
-    base = model.module if hasattr(model, 'module') else model
-    if getattr(base, 'accepts_text_lens', False) and torch.is_tensor(image_batch[2]) and not image_batch[2].is_cuda:
+    if getattr(unwrap(model), 'accepts_text_lens', False) and torch.is_tensor(image_batch[2]) and not image_batch[2].is_cuda:
         # caption lengths, read off the CPU batch before it is uploaded: the towers then run on unpadded token rows
         # (xfm_amd.packing) without ever asking the device for a size
         from .packing import lens_from_mask
         extra['text_lens'] = lens_from_mask(image_batch[2])
-    text_ids, text_atts, text_ids_masked, masked_pos, masked_ids = (_to(device, t) for t in image_batch[1:])
+    text_ids, text_atts, text_ids_masked, masked_pos, masked_ids = (to_device(device, t) for t in image_batch[1:])
     loss = model(image, text_ids, text_atts, text_ids_masked=text_ids_masked, masked_pos=masked_pos, masked_ids=masked_ids,
                  ret_match_loss=ret_match_loss, ret_mim_loss=ret_mim_loss, ret_mlm_loss=ret_mlm_loss, ret_itc_loss=ret_itc_loss,
                  data_source=data_source, **extra)
@@ -145,9 +104,9 @@ def run_region_iter(model, region_batch, optimizer, accelerator, metric_logger, 
                     ret_match_loss=True, ret_mlm_loss=True, ret_itc_loss=True):
     """Pretrain.py:94-121: one region batch (bs samples over fewer images) through the model with the box losses, backward, and NO
     optimizer step -- the gradients accumulate into the image iteration that follows.  `config` is the global the reference reads."""
-    image = _to(device, region_batch[0])
+    image = to_device(device, region_batch[0])
     idx_to_group_img, text_ids, text_atts, text_ids_masked, masked_pos, masked_ids, image_atts, target_bbox, is_image = \
-        (_to(device, t) for t in region_batch[1:])
+        (to_device(device, t) for t in region_batch[1:])
     if config['calc_image_bbox_loss']:
         is_image = None
     loss = model(image, text_ids, text_atts, text_ids_masked=text_ids_masked, masked_pos=masked_pos, masked_ids=masked_ids,
@@ -161,7 +120,7 @@ def run_region_iter(model, region_batch, optimizer, accelerator, metric_logger, 
 
 def run_text_iter(model, batch, optimizer, accelerator, metric_logger, device):
     """Pretrain.py:124-139: a text-only MLM step with its own optimizer step."""
-    text_ids, text_atts, text_ids_masked, masked_pos, masked_ids = (_to(device, t) for t in batch)
+    text_ids, text_atts, text_ids_masked, masked_pos, masked_ids = (to_device(device, t) for t in batch)
     optimizer.zero_grad()
     loss = model(None, text_ids, text_atts, text_ids_masked=text_ids_masked, masked_pos=masked_pos, masked_ids=masked_ids)
     _backward(accelerator, loss['loss_mlm'], optimizer, True)
@@ -220,11 +179,10 @@ def train(model, image_loader, data_loaders, optimizer, epoch_info, device, sche
             if log is not None:
                 log(global_step, metric_logger.global_avg())
         current_epoch = global_step // step_per_epoch
-        distributed = torch.distributed.is_available() and torch.distributed.is_initialized()
-        if checkpointer is not None and (not distributed or torch.distributed.get_rank() == 0):  # utils.is_main_process()
+        if checkpointer is not None and is_main_process():
             at_epoch = (global_step + 1) % step_per_epoch == 0 and (current_epoch + 1) % config['ckpt_frequent'] == 0
             at_step = (global_step + 1) % config['ckpt_frequent_step'] == 0
-            base = model.module if hasattr(model, 'module') else model
+            base = unwrap(model)
             if at_epoch:
                 # optimizer.state_dict() carries the fused AdamW moments in torch's own per-parameter format
                 # (RCCLDDPAccelerator._publish_optimizer_state), so the reference's save / resume code works unchanged

@@ -13,7 +13,7 @@ What differs, on purpose:
   * the batches carry TOKEN IDS -- a question / answer is an (input_ids, attention_mask) pair where the reference tokenizes strings
     (:48-49, :87, :91); there is no tokenizer and no dataset code on this path.  The test loader's `dataset` holds `answer_list` (the
     strings of the records) and `answer_input` (their ids and mask);
-  * the reference reads the loss with `.item()` after every step (:66); here the loss tensors are parked (pretrain_loop.LossMeters) and
+  * the reference reads the loss with `.item()` after every step (:66); here the loss tensors are parked (task.LossMeters) and
     read when a log line is due;
   * the reference reads two device values per QUESTION (:95-98: `.item()`, `.max()` indexing a Python list); here the model runs with
     `fused=True` -- xfm_answer_shortlist / xfm_answer_rerank -- and writes every question's winning candidate id into ONE device buffer
@@ -24,16 +24,8 @@ import os
 
 import torch
 
-from .pretrain_loop import LossMeters
-
-
-def _read(t):
-    """The loop's single device-to-host read helper (evaluation calls it once per pass; the tests count its calls)."""
-    return t.tolist()
-
-
-def _pair_to(device, t):
-    return tuple(x.to(device, non_blocking=True) for x in t)
+from .task import LossMeters, is_distributed, is_main_process, to_device, unwrap
+from .task import read as _read  # the loop's single device-to-host read (evaluation calls it once per pass; the tests count its calls)
 
 
 def _accumulate_steps(config):
@@ -51,8 +43,7 @@ def train_one_epoch(model, data_loader, optimizer, epoch, device, scheduler, con
     model.train()
     meters = LossMeters()
     for i, (image, question, answer, weights, n) in enumerate(data_loader):
-        image, weights = image.to(device, non_blocking=True), weights.to(device, non_blocking=True)
-        question_input, answer_input = _pair_to(device, question), _pair_to(device, answer)
+        image, weights, question_input, answer_input = to_device(device, (image, weights, question, answer))
         loss = model(image, question_input, answer_input, train=True, k=n, weights=weights)
         meters.update(loss=loss, lr=optimizer.param_groups[0]["lr"])
         accelerator.backward_step(loss, optimizer)
@@ -75,14 +66,13 @@ def evaluation(model, data_loader, device, config):
     A batch is (image, (q_ids, q_atts), question_id).  Returns the reference's list of {"question_id", "answer"} records."""
     model.eval()
     answer_list = data_loader.dataset.answer_list
-    answer_input = _pair_to(device, data_loader.dataset.answer_input)
+    answer_input = to_device(device, data_loader.dataset.answer_input)
     fused = answer_input[0].is_cuda   # (a CPU model path has no kernels to fuse onto)
     # one slot per question: len(loader) batches of at most batch_size_test (a larger batch fails the kernel wrapper's range check)
     winners = torch.zeros(len(data_loader) * config['batch_size_test'], dtype=torch.int64, device=device)
     question_ids, done = [], 0
     for image, question, question_id in data_loader:
-        image = image.to(device, non_blocking=True)
-        question_input = _pair_to(device, question)
+        image, question_input = to_device(device, (image, question))
         n = image.size(0)
         if fused:
             model(image, question_input, answer_input, train=False, k=config['k_test'], fused=True, result=winners, result_offset=done)
@@ -134,8 +124,6 @@ def train(model, train_loader, test_loader, optimizer, device, scheduler, config
     `checkpointer.save_checkpoint(model_state=..., epoch=..., training_states=...)` (optimizer.state_dict() carries the fused AdamW
     moments in torch's format), then from epoch `start_eval` an evaluation pass whose records go to
     <result_dir>/vqa_result_epoch<N>.json.  Returns the list of result files written."""
-    distributed = torch.distributed.is_available() and torch.distributed.is_initialized()
-    main_process = not distributed or torch.distributed.get_rank() == 0
     _accumulate_steps(config)
     results = []
     max_epoch = config['schedular']['epochs']
@@ -144,18 +132,17 @@ def train(model, train_loader, test_loader, optimizer, device, scheduler, config
             train_sampler.set_epoch(epoch)
         train_stats = train_one_epoch(model, train_loader, optimizer, epoch, device, scheduler, config, accelerator, print_freq=print_freq,
                                       log=log)
-        if main_process:
+        if is_main_process():
             log_stats = {**{f'train_{k}': v for k, v in train_stats.items()}, 'epoch': epoch}
             with open(os.path.join(output_dir, "log.txt"), "a") as f:
                 f.write(json.dumps(log_stats) + "\n")
-            model_without_ddp = model.module if hasattr(model, 'module') else model
-            save_obj = {'model': model_without_ddp.state_dict(), 'config': config}
+            save_obj = {'model': unwrap(model).state_dict(), 'config': config}
             if checkpointer is not None:
                 checkpointer.save_checkpoint(model_state=save_obj, epoch=epoch, training_states=optimizer.state_dict())
         if epoch >= config['start_eval']:
             vqa_result = evaluation(model, test_loader, device, config)
-            if main_process:   # (one node: every rank ranks the whole synthetic test set; collect_result's gather is not needed)
+            if is_main_process():   # (one node: every rank ranks the whole synthetic test set; collect_result's gather is not needed)
                 results.append(save_result(vqa_result, result_dir, 'vqa_result_epoch%d' % epoch))
-        if distributed:
+        if is_distributed():
             torch.distributed.barrier()
     return results
