@@ -303,6 +303,28 @@ def test_kernel_sources_set_the_lds_attribute_once_and_include_at_the_top():
         assert {l.split('"')[1] for l in lines if l.startswith('#include "')} >= {f for f in text if f.startswith(host[:-4] + "_")}, host
 
 
+def test_every_kernel_file_is_included_from_capi_exactly_once():
+    """The library is one translation unit: a csrc/*.hip that capi.hip does not reach through #include lines is dead code that the build
+    never notices (and that is_stale() keeps rebuilding for), one reached twice defines its kernels twice.  Read from the include lines
+    alone; the headers carry `#pragma once` and may be named by every file."""
+    csrc = os.path.join(ROOT, "xfm_amd", "csrc")
+    times = {}
+
+    def walk(name):
+        with open(os.path.join(csrc, name)) as f:
+            lines = f.readlines()
+        for line in lines:
+            m = re.match(r'\s*#\s*include\s+"([^"]+)"', line)
+            if m and m.group(1).endswith(".hip"):
+                assert "/" not in m.group(1), (name, m.group(1))
+                times[m.group(1)] = times.get(m.group(1), 0) + 1
+                if times[m.group(1)] == 1:
+                    walk(m.group(1))
+
+    walk("capi.hip")
+    assert times == {f: 1 for f in os.listdir(csrc) if f.endswith(".hip") and f != "capi.hip"}, times
+
+
 # (query, arguments, bytes): the answers of the library BEFORE one plan served the query and the launch (the ladder of xfm_gemm_tn written
 # twice, the batched hint twice, the K-slice rule twice), recorded from it.  Host-only calls; without a device the CU count reads 256.
 GEMM_WORKSPACE_TABLE = [

@@ -1,6 +1,6 @@
 """Statistics of the REAL reference's block-wise MIM mask generator (models/masking_generator.py:27-105) -> tests/golden/mim_mask_stats.npz:
 per-patch mask frequency, the histogram of how many new patches each accepted block added, the histogram of the number of grid rows a
-mask touches and the 2-point co-occurrence at offsets (0,1), (1,0), (1,1) -- what the device sampler (csrc/elementwise.hip
+mask touches and the 2-point co-occurrence at offsets (0,1), (1,0), (1,1) -- what the device sampler (csrc/mim.hip
 mim_masks_kernel) is pinned against.  Runs in the build container only; the reference file is loaded where it lies (it imports
 random / math / numpy only)."""
 import importlib.util

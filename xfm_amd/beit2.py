@@ -63,7 +63,7 @@ class BlockMaskGenerator:
         return flat
 
     def batch(self, n, device=None):
-        """[n, h*w] bool.  On a HIP device the masks are DRAWN there (csrc/elementwise.hip mim_masks_kernel: one wavefront per image
+        """[n, h*w] bool.  On a HIP device the masks are DRAWN there (csrc/mim.hip mim_masks_kernel: one wavefront per image
         runs the same rejection loop with a counter-based generator; ~10 us for a batch instead of n Python rejection loops on the
         thread that also enqueues the step's kernels, beit2.py:432-439 of the reference).  On the CPU: the numpy sampler."""
         if device is not None and torch.device(device).type == "cuda":

@@ -35,22 +35,6 @@ __device__ __forceinline__ void answer_sort_desc(unsigned long long* keys, int n
   }
 }
 
-// block-wide max / sum over the 256 lanes (red: 4 floats of LDS); every lane gets the result
-__device__ __forceinline__ float answer_block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();   // (earlier readers of red are done)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ float answer_block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // Dynamic LDS: n_pad keys (8 bytes each), then 4 floats.  vec: every row starts on 16 bytes (ld % 4 == 0, aligned base).
 // Two passes over the row (max, then sum of expf(x - max) with the accurate expf: the probabilities are compared against fp64 softmax
 // at the resolution of fp32 arithmetic, which __expf's argument scaling does not keep for |x - max| ~ 100); the row is 200 KB at the
@@ -71,14 +55,14 @@ __global__ __launch_bounds__(ANSWER_THREADS) void answer_shortlist_kernel(const 
     m = fmaxf(m, fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3])));
   }
   for (int c = Vv + tid; c < V; c += ANSWER_THREADS) m = fmaxf(m, x[c]);
-  m = answer_block_max(m, red);
+  m = block_max256(m, red);
   float s = 0.f;
   for (int c = tid * 4; c < Vv; c += ANSWER_THREADS * 4) {
     const f32x4 a = *reinterpret_cast<const f32x4*>(x + c);
     s += (expf(a[0] - m) + expf(a[1] - m)) + (expf(a[2] - m) + expf(a[3] - m));
   }
   for (int c = Vv + tid; c < V; c += ANSWER_THREADS) s += expf(x[c] - m);
-  s = answer_block_sum(s, red);
+  s = block_sum256(s, red);
   for (int a = tid; a < n_pad; a += ANSWER_THREADS) {
     unsigned long long key = 0ull;
     if (a < A) {
@@ -115,10 +99,10 @@ __global__ __launch_bounds__(ANSWER_THREADS) void answer_rerank_kernel(const flo
     score[j] = sc;
     m = fmaxf(m, sc);
   }
-  m = answer_block_max(m, red);
+  m = block_max256(m, red);
   float s = 0.f;
   for (int j = tid; j < k; j += ANSWER_THREADS) s += expf(score[j] - m);   // (each lane reads back its own entries)
-  s = answer_block_sum(s, red);
+  s = block_sum256(s, red);
   for (int j = tid; j < n_pad; j += ANSWER_THREADS) keys[j] = j < k ? answer_key(expf(score[j] - m) / s, j) : 0ull;
   __syncthreads();
   answer_sort_desc(keys, n_pad);
@@ -143,7 +127,7 @@ int xfm_answer_shortlist_impl(const float* logits, long ld, int Q, int V, const 
   XFM_REQUIRE(A >= 1 && A <= XFM_ANSWER_MAX_A, "answer_shortlist: A=%d outside [1, %d]", A, XFM_ANSWER_MAX_A);
   XFM_REQUIRE(k >= 1 && k <= A && k <= XFM_ANSWER_MAX_K, "answer_shortlist: k=%d outside [1, min(A=%d, %d)]", k, A, XFM_ANSWER_MAX_K);
   const int n_pad = answer_pow2(A);
-  const int vec = (ld & 3) == 0 && ((uintptr_t)logits & 15) == 0 ? 1 : 0;
+  const int vec = rows_aligned16(logits, ld) ? 1 : 0;
   constexpr int MAX_LDS = XFM_ANSWER_MAX_A * 8 + 16;
   lds_launch<answer_shortlist_kernel, MAX_LDS>(dim3(Q), dim3(ANSWER_THREADS), (size_t)n_pad * 8 + 16, st, logits, ld, V, first_tok, A, k, n_pad,
                                                vec, prob, cand);

@@ -33,10 +33,15 @@ int xfm_cu_count() {
 #include "gemm.hip"
 #include "layernorm.hip"
 #include "attention.hip"
-#include "elementwise.hip"
+#include "vit_input.hip"
+#include "mim.hip"
+#include "embedding.hip"
+#include "cross_entropy.hip"
+#include "optimizer.hip"
+#include "rows.hip"
 #include "encoder.hip"
-#include "losses.hip"
-#include "losses_soft.hip"
+#include "contrastive.hip"
+#include "mixup.hip"
 #include "region.hip"
 #include "answer_rank.hip"
 #include "dp.hip"

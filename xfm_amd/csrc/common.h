@@ -15,6 +15,7 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 #define XFM_INTERNAL_BF16
 #include "../../include/xfm_hip.h"
+#include "reduce.h"   // wave_sum / wave_max / block_*256, aligned16
 
 #define LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
 #define GLB_PTR(T, p) ((const __attribute__((address_space(1))) T*)(p))
@@ -96,17 +97,6 @@ __device__ __forceinline__ uint32_t rng_row_key(uint32_t seed_lo, uint32_t seed_
 __device__ __forceinline__ uint32_t rng_u32(uint32_t row_key, uint32_t col) { return mix32(col + row_key); }
 // keep with probability (1-p): thresh = p * 2^32
 __device__ __forceinline__ bool rng_keep(uint32_t r, uint32_t thresh) { return r >= thresh; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // Bijective XCD-aware block remap: blocks b and b+8 share an XCD (round-robin dispatch), so give each
 // XCD a contiguous chunk of the logical tile space (speed only, never correctness).

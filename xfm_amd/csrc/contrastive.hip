@@ -24,21 +24,6 @@ __device__ __forceinline__ void row_logits(const float* __restrict__ own, const 
   __syncthreads();
 }
 
-__device__ __forceinline__ float block_max256(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ float block_add256(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // the logits row lives in dynamic LDS (N floats + 4 reduction slots): 16000 rows = 62.5 KiB, inside the default 64 KiB dynamic limit.
 // The gathered row count is world_size * B (the reference pre-trains at 128 x 24 = 3072).
 #define XFM_LOSS_MAXN 16000
@@ -61,14 +46,14 @@ __global__ __launch_bounds__(256) void itc_fwd_kernel(const float* __restrict__ 
   mx = block_max256(mx, red);
   float s = 0.f;
   for (int j = threadIdx.x; j < N; j += 256) s += __expf(lg[j] - mx);
-  s = block_add256(s, red);
+  s = block_sum256(s, red);
   float pos = 0.f, npos = 0.f;
   if (idx != nullptr) {
     const int64_t mine = idx[r];
     for (int j = threadIdx.x; j < N; j += 256)
       if (idx[j] == mine) { pos += lg[j]; npos += 1.f; }
-    pos = block_add256(pos, red);
-    npos = block_add256(npos, red);
+    pos = block_sum256(pos, red);
+    npos = block_sum256(npos, red);
   }
   // The loss is the sum of the 2N row terms in a FIXED order (a float atomicAdd per block made two runs of the same step differ in the
   // last bit of loss_itc): every block parks its term behind the statistics (lse[2N + block]); the block that takes the last ticket
@@ -87,7 +72,7 @@ __global__ __launch_bounds__(256) void itc_fwd_kernel(const float* __restrict__ 
   __threadfence();
   float t = 0.f;
   for (int j = threadIdx.x; j < 2 * N; j += 256) t += __builtin_nontemporal_load(lse + 2 * N + j);
-  t = block_add256(t, red);
+  t = block_sum256(t, red);
   if (threadIdx.x == 0) loss_sum[0] += t;
 }
 
@@ -123,7 +108,7 @@ __global__ __launch_bounds__(256) void itc_bwd_kernel(const float* __restrict__ 
   }
   __syncthreads();
   if (rows) {
-    tpart = block_add256(tpart, red);
+    tpart = block_sum256(tpart, red);
     // (the row's share of the temperature gradient is parked behind the statistics -- lse[2N + r], the forward's dead row terms -- and
     // itc_dtemp_kernel adds the N shares in a fixed order: a float atomic per row made `temp`'s gradient differ from run to run)
     if (threadIdx.x == 0) const_cast<float*>(lse)[2 * N + r] = -tpart * gs * inv_temp;
@@ -151,7 +136,7 @@ __global__ __launch_bounds__(256) void hard_neg_kernel(const float* __restrict__
   mx = block_max256(mx, red);
   float s = 0.f;
   for (int j = threadIdx.x; j < B; j += 256) s += __expf(lg[j] - mx);
-  s = block_add256(s, red);
+  s = block_sum256(s, red);
   const float inv = 1.0f / s;
   float wsum = 0.f;
   for (int j = threadIdx.x; j < B; j += 256) {
@@ -161,7 +146,7 @@ __global__ __launch_bounds__(256) void hard_neg_kernel(const float* __restrict__
     lg[j] = wj;
     wsum += wj;
   }
-  wsum = block_add256(wsum, red);
+  wsum = block_sum256(wsum, red);
   if (threadIdx.x == 0) {  // one categorical draw by the inverse CDF (B <= a few hundred: a serial scan)
     const uint32_t key = rng_row_key(seed_lo, seed_hi, blockIdx.x);
     const float u = (float)(rng_u32(key, 0u) >> 8) * (1.0f / 16777216.0f) * wsum;
@@ -204,6 +189,15 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const float* __restric
   for (int k = 0; k < EPL; ++k) dx[(long)row * E + k * 64 + lane] = (a[k] - b[k] * s) * iv;
 }
 
+__global__ __launch_bounds__(256) void itc_dtemp_kernel(const float* __restrict__ share, int N, float* __restrict__ dtemp) {
+  __shared__ float red[4];
+  float t = 0.f;
+  for (int j = threadIdx.x; j < N; j += 256) t += share[j];
+  t = block_sum256(t, red);
+  if (threadIdx.x == 0) dtemp[0] += t;
+}
+
+// ---- host side ----
 #define XFM_EPL_DISPATCH(E, CALL)                                                        \
   switch ((E) / 64) {                                                                    \
     case 1: { constexpr int EPL = 1; CALL; break; }                                      \
@@ -237,13 +231,6 @@ int xfm_itc_fwd_impl(const float* I, const float* T, const float* temp, int N, i
   XFM_REQUIRE(idx == nullptr || cnt != nullptr, "itc_fwd: idx needs the cnt output");
   XFM_EPL_DISPATCH(E, hipLaunchKernelGGL((itc_fwd_kernel<EPL>), dim3(2 * N), dim3(256), (N + 4) * sizeof(float), st, I, T, temp, N, E, lse, loss_sum, idx, cnt));
   return xfm_check_launch("itc_fwd");
-}
-__global__ __launch_bounds__(256) void itc_dtemp_kernel(const float* __restrict__ share, int N, float* __restrict__ dtemp) {
-  __shared__ float red[4];
-  float t = 0.f;
-  for (int j = threadIdx.x; j < N; j += 256) t += share[j];
-  t = block_add256(t, red);
-  if (threadIdx.x == 0) dtemp[0] += t;
 }
 
 int xfm_itc_bwd_impl(const float* I, const float* T, const float* temp, const float* lse, const float* g, int N, int E, float* dI,

@@ -124,14 +124,6 @@ static int ln_grid(int rows) {
 // Wide rows (D a multiple of 1024 up to 8192, PLAIN mode): the 3072 / 6144-wide LayerNorms of the classification head
 // (model_classification.py:33-48).  One 256-thread workgroup per row, the row stays in registers (<= 8 x 4 values per thread),
 // block reductions through LDS.  Few rows (one per sample), so no attempt at the multi-row tiling of the main kernels.
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 __global__ __launch_bounds__(256) void ln_wide_fwd_kernel(LnFwd p, int D) {
   __shared__ float red[4];
   const int row = blockIdx.x, nv = D / 1024;
@@ -149,11 +141,11 @@ __global__ __launch_bounds__(256) void ln_wide_fwd_kernel(LnFwd p, int D) {
     }
     for (int j = 0; j < 4; ++j) s += v[i][j];
   }
-  const float mu = block_sum256(s, red) / D;
+  const float mu = block_sum256_serial(s, red) / D;
   float q = 0.f;
   for (int i = 0; i < nv; ++i)
     for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mu; q += d * d; }
-  const float rstd = rsqrtf(block_sum256(q, red) / D + p.eps);
+  const float rstd = rsqrtf(block_sum256_serial(q, red) / D + p.eps);
   if (threadIdx.x == 0) { p.mean[row] = mu; p.rstd[row] = rstd; }
   for (int i = 0; i < nv; ++i) {
     const int e = (i * 256 + threadIdx.x) * 4;
@@ -569,8 +561,8 @@ __global__ __launch_bounds__(256) void ln_wide_bwd_kernel(LnBwd p, int D, float*
       if (dbeta != nullptr) atomicAdd(dbeta + e + j, dy[i][j]);
     }
   }
-  c1 = block_sum256(c1, red) / D;
-  c2 = block_sum256(c2, red) / D;
+  c1 = block_sum256_serial(c1, red) / D;
+  c2 = block_sum256_serial(c2, red) / D;
   for (int i = 0; i < nv; ++i) {
     const int e = (i * 256 + threadIdx.x) * 4;
     const f32x4 w = *reinterpret_cast<const f32x4*>(p.w + e);

@@ -40,7 +40,7 @@ def create_optimizer(args, model):
           {"params": [params[n] for n in g[3]], "weight_decay": 0.0, "lr": lr * lr_mult}]
     # transformers' AdamW of the reference = decoupled weight decay applied after the Adam update, bias correction on, eps added to
     # sqrt(v) before the correction.  RCCLDDPAccelerator runs exactly that rule as one fused kernel over the flat arena
-    # (csrc/elementwise.hip adamw_kernel); this torch.optim.AdamW object carries the groups / hyper-parameters / state_dict and is
+    # (csrc/optimizer.hip adamw_kernel); this torch.optim.AdamW object carries the groups / hyper-parameters / state_dict and is
     # the stepping rule only where the fused path is off (CPU): there eps enters after the correction (differs for |g| ~ 1e-8)
     return torch.optim.AdamW(pg, lr=lr, eps=1e-8, betas=(0.9, 0.98))
 
