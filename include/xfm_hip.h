@@ -47,7 +47,9 @@ int xfm_gemm_nt(const xfm_bf16* A, long lda, const xfm_bf16* B, long ldb, void* 
 
 /* The launch plan xfm_gemm_nt follows for a shape (profilers / benchmarks attribute a call to its kernels with it): *cfg = tile
  * configuration (the tile_hint numbering), *rows_a > 0 = tail split: the leading rows_a rows run as whole rounds of 256x256 tiles
- * (configuration 5), the remaining rows are planned again with tile_hint -1. */
+ * (configuration 5), the remaining rows are planned again with tile_hint -1.  This is the plan of tight operands (lda = ldb = K):
+ * configuration 5 addresses its operands with 32-bit element offsets, so a call whose M * lda or N * ldb reaches 2^32 runs
+ * configuration 1 wherever this plan says 5 for tile_hint 0 or for the tail split; an explicit tile_hint 5 is then an error. */
 int xfm_gemm_nt_plan(int M, int N, int K, int epilogue, int tile_hint, int* cfg, int* rows_a);
 
 /* out[M,N] = A[M,K] . B[N,K]^T (+ bias) for a very long K against few output tiles -- the activation gradient of the vocabulary

@@ -22,7 +22,10 @@ static int nt_k_slices(int M, int N, int K) {
 // phase pipeline, 7 = 64x128 on 3 LDS stages, 8 = 64x64 on 4) and, for the tail split, the leading rows that run as whole rounds of
 // 256x256 tiles (rows_a > 0: those rows go to configuration 5, the rest is planned again with hint -1).  Exported as
 // xfm_gemm_nt_plan so that a profiler / benchmark can attribute a call to the kernels it launches.
-static int nt_plan(int M, int N, int K, int epi, int tile_hint, int* rows_a_out, int* k_splits_out) {
+// The leading dimensions take part: the 256x256 kernel addresses its operands with 32-bit element offsets (nt256_eligible,
+// gemm_nt_256.hip), so where the automatic plan or the tail split would pick it for operands past that range it steps down to
+// configuration 1, whose row offsets are 64-bit -- as tn_plan does with tn256_eligible.  An explicit hint 5 is left to fail in the launcher.
+static int nt_plan(int M, int N, int K, long lda, long ldb, int epi, int tile_hint, int* rows_a_out, int* k_splits_out) {
   *rows_a_out = 0;
   *k_splits_out = 1;
   int cfg = tile_hint;
@@ -35,6 +38,7 @@ static int nt_plan(int M, int N, int K, int epi, int tile_hint, int* rows_a_out,
     if (split_env && tile_hint == 0 && M >= 2048 && t256 > 256 && t256 % 256 != 0 && (t256 % 256) * 100 < split_env * 256) {
       const int rows_a = (int)((t256 / 256) * 256 / tn256) * 256;  // row tiles that exactly fill the whole rounds
       if (rows_a > 0 && rows_a < M) {
+        if (!nt256_eligible(rows_a, lda, N, ldb)) return 1;
         *rows_a_out = rows_a;
         return 5;
       }
@@ -42,7 +46,7 @@ static int nt_plan(int M, int N, int K, int epi, int tile_hint, int* rows_a_out,
     // ~half a round of 256x256 tiles already beats the rest on the tall problems (M = 12608 / 25216); on the packed token rows of
     // the text / fusion towers (M ~ 2600 .. 5300, tools/tune_small.py) it needs ~0.7 of a round, below that 128x128 tiles win
     // (5248x1536x768: 25.2 -> 17.4 us, 2624x3072x768: 24.0 -> 17.1 us)
-    if (M >= 2048 && (t256 >= 180 || (t256 >= 120 && M >= 8192))) cfg = 5;
+    if (M >= 2048 && (t256 >= 180 || (t256 >= 120 && M >= 8192))) cfg = nt256_eligible(M, lda, N, ldb) ? 5 : 1;
     else if (M >= 2048 && t256 >= 120) cfg = 1;
     else if ((long)cdiv(M, 256) * cdiv(N, 128) >= 768) cfg = 4;  // >= 3 rounds of 256x128 tiles: the 3-slot ring wins on cold operands
     else if ((long)cdiv(M, 128) * cdiv(N, 128) >= 800) cfg = 1;
@@ -69,7 +73,7 @@ static int nt_plan(int M, int N, int K, int epi, int tile_hint, int* rows_a_out,
 int xfm_gemm_nt_plan_impl(int M, int N, int K, int epi, int tile_hint, int* cfg, int* rows_a) {
   XFM_REQUIRE(M > 0 && N > 0 && K > 0 && cfg != nullptr && rows_a != nullptr, "gemm_nt_plan: bad arguments");
   int ks = 1;
-  *cfg = nt_plan(M, N, K, epi, tile_hint, rows_a, &ks);
+  *cfg = nt_plan(M, N, K, K, K, epi, tile_hint, rows_a, &ks);   // the plan of tight operands (lda = ldb = K)
   return XFM_OK;
 }
 
@@ -98,7 +102,7 @@ int xfm_gemm_nt_impl(const void* A, long lda, const void* B, long ldb, void* C, 
   GemmNT g = gemm_nt_args(A, lda, B, ldb, C, ldc, bias, M, N, K);
   g.aux = (bf16*)aux; g.ldaux = ldaux;
   int rows_a = 0, k_splits = 1;
-  const int cfg = nt_plan(M, N, K, epi, tile_hint, &rows_a, &k_splits);
+  const int cfg = nt_plan(M, N, K, lda, ldb, epi, tile_hint, &rows_a, &k_splits);
   if (rows_a > 0) {  // tail split: whole rounds of 256x256 tiles first, the remaining rows on the small-tile kernels
     int rc = xfm_gemm_nt_impl(A, lda, B, ldb, C, ldc, bias, aux, ldaux, rows_a, N, K, epi, 5, st);
     if (rc != XFM_OK) return rc;

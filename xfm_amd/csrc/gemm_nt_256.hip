@@ -276,6 +276,11 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(GemmNT g, int tiles) {
 }
 
 // ---- host side ----
+// the kernel's per-lane staging offsets (row * ld + chunk) are 32-bit element offsets
+static bool nt256_eligible(int M, long lda, int N, long ldb) {
+  return (unsigned long)M * (unsigned long)lda < (1ul << 32) && (unsigned long)N * (unsigned long)ldb < (1ul << 32);
+}
+
 #ifdef XFM_DIAG
 // Diagnostic build: where the next launches of the 256 x 256 kernel put their stamps (xfm_diag_set_timeline, capi.hip); ptr NULL = off
 static XfmTimeline nt256_timeline = {nullptr, 0, 0};
@@ -284,7 +289,7 @@ static XfmTimeline nt256_timeline = {nullptr, 0, 0};
 static int launch_nt_256(const GemmNT& g_in, int epi, hipStream_t st) {
   GemmNT g = g_in;
   const int tiles = cdiv(g.M, 256) * cdiv(g.N, 256);
-  if ((unsigned long)g.M * (unsigned long)g.lda >= (1ul << 32) || (unsigned long)g.N * (unsigned long)g.ldb >= (1ul << 32)) {
+  if (!nt256_eligible(g.M, g.lda, g.N, g.ldb)) {
     xfm_set_error("gemm_nt: operand too large for the 256x256 kernel's 32-bit element offsets");
     return XFM_E_ARG;
   }
