@@ -1,7 +1,8 @@
 """Kernel-level parity on a real MI355X: every C-ABI entry point against plain fp32 PyTorch math on the same inputs.
 Tolerances: inputs are bf16 (exact products), accumulation fp32; outputs that are stored as bf16 carry one rounding
 (bf16's unit roundoff, 2^-8 relative).  GEMM / attention results are compared at <= 1e-2 of the tensor's max |value| (abs) -- stated per test.
-Elementwise fp64 bounds for the LayerNorm and cross-entropy kernels live in tests/test_hip_layernorm_bounds.py and tests/test_hip_ce_bounds.py."""
+Elementwise fp64 bounds for the LayerNorm and cross-entropy kernels live in tests/test_hip_layernorm_bounds.py and tests/test_hip_ce_bounds.py,
+those for the attention routes with a key mask, a causal mask or dropout in tests/test_hip_attention_bounds.py."""
 import math
 
 import pytest
