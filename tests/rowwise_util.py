@@ -159,12 +159,15 @@ def ln_fwd_ref(x, w, b, eps, x_err=None, gelu=False):
 
 
 # ----------------------------------------------------------------------------------------------------------------- LayerNorm backward
-def ln_bwd_ref(dy_parts, x, mean, rstd, w, gelu_b=None):
+def ln_bwd_ref(dy_parts, x, mean, rstd, w, gelu_b=None, dy_err=None):
     """dy_parts: the tensors the kernel adds up to dy (dy1, dy2, dy32; None entries skipped); x the normalised row as stored; mean / rstd the
-    fp32 statistics handed to the kernel.  Returns a dict: dx (ref, bound), dy (the activated gradient, its error bound), xh."""
+    fp32 statistics handed to the kernel; dy_err: a bound on further roundings the caller's kernel makes on dy (the embedding's dropout
+    product).  Returns a dict: dx (ref, bound), dy (the activated gradient, its error bound), xh."""
     parts = [p.double() for p in dy_parts if p is not None]
     DY = sum(parts)
     e_dy = (len(parts) - 1) * U32 * sum(p.abs() for p in parts) if len(parts) > 1 else torch.zeros_like(DY)
+    if dy_err is not None:
+        e_dy = e_dy + dy_err
     X, W = x.double(), w.double()
     D = X.shape[1]
     rs = rstd.double().unsqueeze(1)

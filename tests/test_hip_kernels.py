@@ -2,7 +2,9 @@
 Tolerances: inputs are bf16 (exact products), accumulation fp32; outputs that are stored as bf16 carry one rounding
 (bf16's unit roundoff, 2^-8 relative).  GEMM / attention results are compared at <= 1e-2 of the tensor's max |value| (abs) -- stated per test.
 Elementwise fp64 bounds for the LayerNorm and cross-entropy kernels live in tests/test_hip_layernorm_bounds.py and tests/test_hip_ce_bounds.py,
-those for the attention routes with a key mask, a causal mask or dropout in tests/test_hip_attention_bounds.py."""
+those for the attention routes with a key mask, a causal mask or dropout in tests/test_hip_attention_bounds.py.
+The embedding kernels have theirs in tests/test_hip_embedding_bounds.py, the row moves, the ViT input kernels and the MIM loss in
+tests/test_hip_token_rows_bounds.py."""
 import math
 
 import pytest
