@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 14
+#define XFM_ABI_VERSION 15
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -531,6 +531,37 @@ int xfm_answer_shortlist(const float* logits, long ld, int Q, int V, const int64
                          void* stream);
 int xfm_answer_rerank(const float* prob, const float* seq_loss, const int64_t* cand, int Q, int k, int64_t* topk_ids, float* topk_probs,
                       int64_t* result, long result_offset, void* stream);
+
+/* ---- GLUE evaluation metrics and the regression loss (run_glue.py:370-386; model_classification.py:89-93; ABI 15) -----------------------
+ * Plain loads and stores, no float atomics, no global atomics: the same bits with and without XFM_DETERMINISTIC.  Any ld / stride and
+ * any base alignment of the fp32 / bf16 operands (int64 and double operands lie on 8 bytes).
+ *
+ * xfm_cls_eval (`outputs.argmax(dim=-1)` + `metric.add_batch`, :380-384): logits fp32 [B, ld] with L live columns, labels int64 [B].
+ * Per row r: p = argmax under TORCH.ARGMAX'S RULE -- the first index of the maximum; a NaN counts as the maximum and the first NaN wins;
+ * -0.0 == +0.0.  pred[pred_offset + r] = p (pred int64, may be NULL).  If 0 <= labels[r] < L: conf[labels[r] * L + p] += 1; a row with
+ * any other label (GLUE's test splits carry -1) is written to pred and counted nowhere.  conf int64 [L * L] ACCUMULATES across calls: zero
+ * it once per pass, read it once at the end.  One workgroup owns conf for the call (integer counts: the order of the adds cannot
+ * change them).  XFM_E_ARG (nothing is launched): B < 1, L < 2, L > XFM_METRIC_MAX_L, ld < L, pred_offset < 0, NULL logits / labels / conf.
+ *
+ * xfm_corr_rank (pearsonr / spearmanr of the glue metric for stsb): x, y fp32 [N] -> out double [2] = (Pearson, Spearman); rank_x,
+ * rank_y fp32 [N] (each may be NULL) receive the average ranks.  One workgroup.  Pearson: fp64, two passes (means, then centred sums),
+ * every sum in a fixed order, r = Sxy / sqrt(Sxx * Syy); a zero denominator gives NaN, as scipy.  Spearman: the same formula on AVERAGE
+ * RANKS as scipy.stats.rankdata(method='average') defines them -- equal values share the mean of their 1-based positions (every rank is
+ * a multiple of 0.5); -0.0 and +0.0 are equal.  The values are sorted in LDS (bitonic network, 64-bit unique keys: an order-preserving
+ * image of the float above the position), which sets the cap.  Any NaN in x or y makes both outputs (and the ranks) NaN.
+ * XFM_E_ARG: N < 2, N > XFM_CORR_MAX_N, NULL x / y / out.
+ *
+ * xfm_mse_fwd / xfm_mse_bwd (`F.mse_loss(prediction.view(-1), targets.view(-1))`): pred fp32 or bf16 (pred_bf16 != 0), element i at
+ * pred[i * stride]; target fp32 [B].  fwd: loss[0] = sum_i (p_i - t_i)^2 / B in fp32, one workgroup, ordered sum.
+ * bwd: dpred fp32 [B] (contiguous), dpred[i] = 2 * dloss[0] * (p_i - t_i) / B with dloss a DEVICE scalar (no host read).
+ * XFM_E_ARG: B < 1, stride < 1, a NULL operand. */
+#define XFM_METRIC_MAX_L 32
+#define XFM_CORR_MAX_N 8192
+int xfm_cls_eval(const float* logits, long ld, int B, int L, const int64_t* labels, int64_t* conf, int64_t* pred, long pred_offset,
+                 void* stream);
+int xfm_corr_rank(const float* x, const float* y, int N, double* out, float* rank_x, float* rank_y, void* stream);
+int xfm_mse_fwd(const void* pred, long stride, int pred_bf16, const float* target, int B, float* loss, void* stream);
+int xfm_mse_bwd(const void* pred, long stride, int pred_bf16, const float* target, const float* dloss, int B, float* dpred, void* stream);
 
 /* ---- Device Mixup / CutMix (timm Mixup._mix_batch / _mix_elem and mixup_target as called at Imagenet.py:468-469; ABI 10) -------------
  * xfm_mixup: fp32 images [B, C, H, W], B even, mixed IN PLACE: row i against the original row j = B - 1 - i, with the per-row device

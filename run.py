@@ -4,6 +4,7 @@
     python3 run.py --task pretrain_DIY --dist 1 --config configs/Pretrain_synthetic.yaml --output_dir output/pt
     python3 run.py --task imagenet --dist gpu0 --config configs/Imagenet_synthetic.yaml --output_dir output/in
     python3 run.py --task vqa --dist 1 --config configs/VQA_synthetic.yaml --output_dir output/vqa [--evaluate]
+    python3 run.py --task glue --dist gpu0 --config configs/glue_synthetic.yaml --output_dir output/glue
 
 `--dist` follows run.py:44-75: '1' / 'all' = every visible GPU of this node, 'f4' / 'l4' = the first / last four, 'gpuK' = GPU K
 alone.  The reference builds a `torch.distributed.launch --use_env` shell line and hands it to os.system; here the ranks are started
@@ -20,9 +21,9 @@ if ROOT not in sys.path:
 
 from xfm_amd.launch import launch, launch_command, visible_gpu_count  # noqa: E402
 
-TASK_SCRIPTS = {"pretrain_DIY": "Pretrain.py", "imagenet": "Imagenet.py", "vqa": "VQA.py"}
+TASK_SCRIPTS = {"pretrain_DIY": "Pretrain.py", "imagenet": "Imagenet.py", "vqa": "VQA.py", "glue": "run_glue.py"}
 DEFAULT_CONFIGS = {"pretrain_DIY": "configs/Pretrain_synthetic.yaml", "imagenet": "configs/Imagenet_synthetic.yaml",
-                   "vqa": "configs/VQA_synthetic.yaml"}
+                   "vqa": "configs/VQA_synthetic.yaml", "glue": "configs/glue_synthetic.yaml"}
 
 
 def get_dist(args, n_visible=None):
@@ -49,7 +50,7 @@ def task_command(args, n_visible=None):
     if not args.config or not os.path.exists(args.config):
         args.config = os.path.join(ROOT, DEFAULT_CONFIGS[args.task])
     nproc, vis = get_dist(args, n_visible)
-    if args.task == "imagenet":   # run.py:275-287: no --bs, no --epoch
+    if args.task in ("imagenet", "glue"):   # run.py:275-287 (imagenet), run.py:263-272 (glue): no --bs, no --epoch
         script_args = ["--config", args.config, "--output_dir", args.output_dir, "--seed", args.seed]
     elif args.task == "vqa":      # run.py:182-193: --bs is the global batch (VQA.py:134-135 divides it), --evaluate is passed on
         script_args = ["--config", args.config, "--output_dir", args.output_dir, "--bs", args.bs, "--seed", args.seed]

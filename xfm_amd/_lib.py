@@ -13,7 +13,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # XFM_HIP_LIB: A/B a differently built library (kernel experiments); the default is the in-tree build.
 LIB_PATH = os.environ.get("XFM_HIP_LIB") or os.path.join(_HERE, "libxfm_hip.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 c_void_p, c_int, c_long, c_float, c_u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_uint32
 
@@ -118,6 +118,7 @@ class AdamWArgs(ctypes.Structure):
 
 MIM_SUMS_FLOATS = 3 + 3 * 512   # XFM_MIM_SUMS_FLOATS
 ANSWER_MAX_A, ANSWER_MAX_K = 8192, 1024   # XFM_ANSWER_MAX_A, XFM_ANSWER_MAX_K
+METRIC_MAX_L, CORR_MAX_N = 32, 8192       # XFM_METRIC_MAX_L, XFM_CORR_MAX_N
 
 
 # name -> (restype, argtypes); mirrors include/xfm_hip.h one to one
@@ -176,6 +177,10 @@ SIGNATURES = {
     "xfm_ce_topk_eval": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "xfm_answer_shortlist": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "xfm_answer_rerank": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "xfm_cls_eval": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "xfm_corr_rank": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "xfm_mse_fwd": (c_int, [c_void_p, c_long, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "xfm_mse_bwd": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "xfm_mixup": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "xfm_mixup_target": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_long, c_void_p]),
     "xfm_region_pool_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -44,6 +44,7 @@ int xfm_cu_count() {
 #include "mixup.hip"
 #include "region.hip"
 #include "answer_rank.hip"
+#include "metrics.hip"
 #include "dp.hip"
 
 #define ST(s) ((hipStream_t)(s))
@@ -320,6 +321,19 @@ int xfm_answer_rerank(const float* prob, const float* seq_loss, const int64_t* c
                       int64_t* result, long result_offset, void* stream) {
   XFM_REQUIRE(prob && seq_loss && cand && topk_ids && topk_probs, "answer_rerank: null operand");
   return xfm_answer_rerank_impl(prob, seq_loss, cand, Q, k, topk_ids, topk_probs, result, result_offset, ST(stream));
+}
+int xfm_cls_eval(const float* logits, long ld, int B, int L, const int64_t* labels, int64_t* conf, int64_t* pred, long pred_offset,
+                 void* stream) {
+  return xfm_cls_eval_impl(logits, ld, B, L, labels, conf, pred, pred_offset, ST(stream));
+}
+int xfm_corr_rank(const float* x, const float* y, int N, double* out, float* rank_x, float* rank_y, void* stream) {
+  return xfm_corr_rank_impl(x, y, N, out, rank_x, rank_y, ST(stream));
+}
+int xfm_mse_fwd(const void* pred, long stride, int pred_bf16, const float* target, int B, float* loss, void* stream) {
+  return xfm_mse_fwd_impl(pred, stride, pred_bf16, target, B, loss, ST(stream));
+}
+int xfm_mse_bwd(const void* pred, long stride, int pred_bf16, const float* target, const float* dloss, int B, float* dpred, void* stream) {
+  return xfm_mse_bwd_impl(pred, stride, pred_bf16, target, dloss, B, dpred, ST(stream));
 }
 int xfm_mixup(float* x, int B, int C, int H, int W, const float* lam, const int* box, void* stream) {
   XFM_REQUIRE(x && lam && box, "mixup: null operand");

@@ -931,6 +931,68 @@ def answer_rerank(prob, seq_loss, cand, result=None, result_offset=0):
     return topk_ids, topk_probs
 
 
+METRIC_MAX_L, CORR_MAX_N = _lib.METRIC_MAX_L, _lib.CORR_MAX_N   # the caps of xfm_cls_eval / xfm_corr_rank (include/xfm_hip.h)
+
+
+def cls_eval(logits, L, labels, conf, pred=None, pred_offset=0):
+    """xfm_cls_eval: logits fp32 [B, ld >= L] (any ld, any base alignment), labels int64 [B]; conf int64 [L * L] += the batch's confusion
+    counts (rows = label, columns = prediction; labels outside [0, L) are counted nowhere); pred (int64 device buffer, optional):
+    pred[pred_offset + r] = argmax of row r under torch.argmax's rule."""
+    for t in (logits, labels, conf):
+        _dev(t)
+    assert logits.dtype == F32 and logits.dim() == 2 and logits.stride(1) == 1
+    B = logits.shape[0]
+    assert labels.dtype == torch.int64 and labels.numel() == B and labels.is_contiguous()
+    assert conf.dtype == torch.int64 and conf.is_contiguous() and conf.numel() == int(L) * int(L)
+    if pred is not None:
+        _dev(pred)
+        assert pred.dtype == torch.int64 and pred.is_contiguous() and (pred_offset < 0 or pred_offset + B <= pred.numel())
+    check(_lib.load().xfm_cls_eval(logits.data_ptr(), logits.stride(0), B, int(L), labels.data_ptr(), conf.data_ptr(), _ptr(pred),
+                                   int(pred_offset), _stream()), "cls_eval")
+    return conf
+
+
+def corr_rank(x, y, ranks=False):
+    """xfm_corr_rank: x, y fp32 [N] (contiguous, any base alignment) -> out fp64 [2] = (Pearson, Spearman on average ranks) on the device;
+    ranks=True: (out, rank_x fp32 [N], rank_y fp32 [N])."""
+    _dev(x)
+    _dev(y)
+    assert x.dtype == F32 and y.dtype == F32 and x.dim() == 1 and x.is_contiguous() and y.is_contiguous() and y.shape == x.shape
+    N = x.numel()
+    out = torch.empty(2, dtype=torch.float64, device=x.device)
+    rx = torch.empty(N, dtype=F32, device=x.device) if ranks else None
+    ry = torch.empty(N, dtype=F32, device=x.device) if ranks else None
+    check(_lib.load().xfm_corr_rank(x.data_ptr(), y.data_ptr(), N, out.data_ptr(), _ptr(rx), _ptr(ry), _stream()), "corr_rank")
+    return (out, rx, ry) if ranks else out
+
+
+def _mse_operands(pred, target):
+    _dev(pred)
+    _dev(target)
+    assert pred.dtype in (F32, BF16) and pred.dim() == 1 and pred.stride(0) >= 1
+    assert target.dtype == F32 and target.is_contiguous() and target.numel() == pred.numel()
+    return pred.numel(), pred.stride(0), int(pred.dtype == BF16)
+
+
+def mse_fwd(pred, target):
+    """xfm_mse_fwd: pred fp32 / bf16 [B] (any element stride), target fp32 [B] -> loss fp32 [1] = mean((pred - target)^2)."""
+    B, stride, is_bf16 = _mse_operands(pred, target)
+    loss = torch.empty(1, dtype=F32, device=pred.device)
+    check(_lib.load().xfm_mse_fwd(pred.data_ptr(), stride, is_bf16, target.data_ptr(), B, loss.data_ptr(), _stream()), "mse_fwd")
+    return loss
+
+
+def mse_bwd(pred, target, dloss):
+    """xfm_mse_bwd: dloss fp32 [1] on the device -> dpred fp32 [B] = 2 * dloss * (pred - target) / B (no host read)."""
+    B, stride, is_bf16 = _mse_operands(pred, target)
+    _dev(dloss)
+    assert dloss.dtype == F32 and dloss.numel() == 1
+    dpred = torch.empty(B, dtype=F32, device=pred.device)
+    check(_lib.load().xfm_mse_bwd(pred.data_ptr(), stride, is_bf16, target.data_ptr(), dloss.data_ptr(), B, dpred.data_ptr(), _stream()),
+          "mse_bwd")
+    return dpred
+
+
 def mixup_(x, lam, box):
     """In-place batch mix (xfm_mixup): x fp32 [B, C, H, W] contiguous, B even; row i against the original row B - 1 - i with lam fp32 [B]
     and box int32 [B, 4] = (yl, yh, xl, xh) on the device (lam 1: untouched; empty box: mixup; else CutMix inside the box) -> x."""

@@ -3,7 +3,7 @@ deep MLP head), text-only GLUE-style classification on the text tower, and the m
 import torch
 import torch.nn.functional as F
 
-from .ops import small_ce
+from .ops import small_ce, small_mse
 from .xfm import XFMBase, _DeepMlp, build_mlp
 
 
@@ -40,7 +40,10 @@ class XFMForClassification(XFMBase):
             output_cls = self.get_cross_embeds(image_embeds, image_atts, text_embeds=encoder_embeds, text_atts=text_atts,
                                                is_pretrain=False)[:, 0, :]
         prediction = self.cls_head(output_cls)
-        if prediction.shape[-1] == 1:
-            loss = F.mse_loss(prediction.view(-1).float(), targets.view(-1).float())
-            return loss if train else prediction
+        if prediction.shape[-1] == 1:   # regression (STS-B, model_classification.py:89-93)
+            if not train:
+                return prediction
+            if prediction.is_cuda:
+                return small_mse(prediction, targets)
+            return F.mse_loss(prediction.view(-1).float(), targets.view(-1).float())
         return small_ce(prediction, targets) if train else prediction

@@ -176,6 +176,33 @@ def small_ce(logits, labels, n_valid=None):
     return _SmallCEFn.apply(logits, labels, n_valid)
 
 
+class _SmallMSEFn(torch.autograd.Function):
+    """F.mse_loss(prediction.view(-1), targets.view(-1)) of the regression head (model_classification.py:89-93, STS-B) as one kernel
+    each way (xfm_mse_fwd / xfm_mse_bwd): fp32 arithmetic on the fp32 / bf16 prediction column read in place (its element stride is
+    passed), the upstream gradient read from the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        p = pred.reshape(-1)   # ([B, 1] -> [B]: a view, also of a strided column)
+        t = target.reshape(-1).to(F32).contiguous()
+        ctx.save_for_backward(p, t)
+        ctx.shape, ctx.dtype = pred.shape, pred.dtype
+        return Fx.mse_fwd(p, t).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        p, t = ctx.saved_tensors
+        d = Fx.mse_bwd(p, t, g.to(F32).reshape(1).contiguous())
+        return d.view(ctx.shape).to(ctx.dtype), None
+
+
+def small_mse(pred, target):
+    """Mean squared error between a prediction column (fp32 / bf16, [B] or [B, 1]) and its targets (any float dtype, B elements)."""
+    if pred.dtype not in (F32, BF16):
+        pred = pred.float()
+    return _SmallMSEFn.apply(pred, target)
+
+
 def gelu_grad(u):
     u = u.float()
     return 0.5 * (1.0 + torch.erf(u * (1.0 / math.sqrt(2.0)))) + u * torch.exp(-0.5 * u * u) * (1.0 / math.sqrt(2.0 * math.pi))

@@ -290,3 +290,21 @@ def vqa_eval_batch(batch_size, seed=1234, image_res=480, max_tokens=40, first_qu
     int64 [B, max_tokens], question_id int64 [B] = first_question_id + 0 .. B - 1)."""
     b = pretrain_batch(batch_size, seed=seed, image_res=image_res, max_tokens=max_tokens)
     return b["image"], (b["text_ids"], b["text_atts"]), torch.arange(first_question_id, first_question_id + batch_size)
+
+
+def glue_batch(batch_size, seed=1234, max_length=128, min_len=8, vocab=VOCAB, pad_id=PAD, num_labels=2):
+    """One GLUE batch as run_glue.py:283's collate emits it (`padding='longest'`): (input_ids int64 [B, T], attention_mask int64 [B, T],
+    labels) with T the longest sequence of THIS batch (<= max_length), `<s> ... </s>` rows padded with pad_id.  Labels: int64 in
+    [0, num_labels) for classification; for num_labels == 1 (STS-B) fp32 similarity scores on a 0.2 grid in [0, 5], so that the label
+    ranks are full of ties."""
+    b = pretrain_batch(batch_size, seed=seed, max_tokens=max_length, min_len=min(min_len, max_length), vocab=vocab, with_image=False)
+    atts = b["text_atts"]
+    T = int(atts.sum(1).max())
+    ids, atts = b["text_ids"][:, :T].clone(), atts[:, :T].clone()
+    ids[atts == 0] = pad_id
+    u = uniform01("glue.label", batch_size, seed)
+    if num_labels == 1:
+        labels = torch.from_numpy((np.minimum(np.floor(u * 26.0), 25.0) / 5.0).astype(np.float32))
+    else:
+        labels = torch.from_numpy(np.minimum((u * num_labels).astype(np.int64), num_labels - 1))
+    return ids, atts, labels
