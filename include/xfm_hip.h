@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 15
+#define XFM_ABI_VERSION 16
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -562,6 +562,25 @@ int xfm_cls_eval(const float* logits, long ld, int B, int L, const int64_t* labe
 int xfm_corr_rank(const float* x, const float* y, int N, double* out, float* rank_x, float* rank_y, void* stream);
 int xfm_mse_fwd(const void* pred, long stride, int pred_bf16, const float* target, int B, float* loss, void* stream);
 int xfm_mse_bwd(const void* pred, long stride, int pred_bf16, const float* target, const float* dloss, int B, float* dpred, void* stream);
+
+/* ---- Grounding evaluation (Grounding_bbox.py:73-93 val; dataset/utils.py:271-345 grounding_eval_bbox / _vlue, :349-361 computeIoU; ABI 16)
+ * xfm_box_eval: the box accuracy of one batch in one launch.  coord fp32 [n, 4] = the model's (cx, cy, w, h) in [0, 1]; ref_row int32 [n]
+ * names each sample's row of the three ref tables (NULL: rows 0 .. n - 1); ref_box fp32 [R, 4] = ground truth (x, y, w, h) in pixels,
+ * ref_size fp32 [R, 2] = (width, height) of the image, ref_split int32 [R] = 0 val, 1 testA, 2 testB (anything else: counted nowhere).
+ * Per sample, in fp64 from the fp32 inputs, every operation rounded on its own, in the reference's order:
+ *   pw = w W, ph = h H, px = cx W - pw / 2, py = cy H - ph / 2                                 (utils.py:281-286)
+ *   x1 = max(rx, px), y1 = max(ry, py), x2 = min(rx + rw - 1, px + pw - 1), y2 = min(ry + rh - 1, py + ph - 1)
+ *   inter = (x2 - x1 + 1)(y2 - y1 + 1) if x1 < x2 and y1 < y2 (both strict), else 0
+ *   union = rw rh + pw ph - inter, IoU = inter / union; union <= 0 (the reference divides by zero): IoU = 0     (utils.py:349-361)
+ *   correct iff IoU >= 0.5.
+ * out fp32 (may be NULL): row out_offset + i = (px, py, pw, ph, IoU), each rounded to fp32 once; the rows of a whole pass collect in ONE
+ * device buffer.  counts int64 [3, 2]: counts[s] += (#correct, #samples) of split s; it ACCUMULATES across calls: zero it once per pass,
+ * read it once at the end.  A ref_row outside [0, R): the out row is NaN and the sample is counted nowhere (nothing is read out of
+ * bounds).  One workgroup owns counts for the call: the six counts are collected in LDS as integers and added with plain 64-bit loads
+ * and stores -- no global atomics, no float atomics, the same bits with and without XFM_DETERMINISTIC.
+ * XFM_E_ARG (nothing is launched): n < 1, R < 1, out_offset < 0, NULL coord / ref_box / ref_size / ref_split / counts. */
+int xfm_box_eval(const float* coord, const int* ref_row, const float* ref_box, const float* ref_size, const int* ref_split, int n, int R,
+                 float* out, long out_offset, int64_t* counts, void* stream);
 
 /* ---- Device Mixup / CutMix (timm Mixup._mix_batch / _mix_elem and mixup_target as called at Imagenet.py:468-469; ABI 10) -------------
  * xfm_mixup: fp32 images [B, C, H, W], B even, mixed IN PLACE: row i against the original row j = B - 1 - i, with the per-row device

@@ -5,11 +5,15 @@
     python3 run.py --task imagenet --dist gpu0 --config configs/Imagenet_synthetic.yaml --output_dir output/in
     python3 run.py --task vqa --dist 1 --config configs/VQA_synthetic.yaml --output_dir output/vqa [--evaluate]
     python3 run.py --task glue --dist gpu0 --config configs/glue_synthetic.yaml --output_dir output/glue
+    python3 run.py --task refcoco_bbox --dist gpu0 --config configs/Grounding_bbox_synthetic.yaml --output_dir output/grd [--evaluate]
 
 `--dist` follows run.py:44-75: '1' / 'all' = every visible GPU of this node, 'f4' / 'l4' = the first / last four, 'gpuK' = GPU K
 alone.  The reference builds a `torch.distributed.launch --use_env` shell line and hands it to os.system; here the ranks are started
 by xfm_amd.launch (torch.distributed.run as a child process, rendezvous on 127.0.0.1) and the launcher's exit code is returned.
-Tasks whose scripts are outside the hot-path scope (captioning, grounding, NLVR data handling ...) raise NotImplementedError, as the
+`refcoco_bbox` is the reference's run_refcoco(use_bbox=True, load_bbox_pretrain=True) (run.py:196-207, :311-318) WITHOUT its first stage:
+the domain pre-training on the refcoco+ boxes (Grounding_bbox_pretrain.py, run.py:108-127, :312) is not part of this launcher, and `--checkpoint`
+is what that stage would have produced.
+Tasks whose scripts are outside the hot-path scope (captioning, mask grounding, NLVR data handling ...) raise NotImplementedError, as the
 reference does for unknown tasks (run.py:352)."""
 import argparse
 import os
@@ -21,9 +25,11 @@ if ROOT not in sys.path:
 
 from xfm_amd.launch import launch, launch_command, visible_gpu_count  # noqa: E402
 
-TASK_SCRIPTS = {"pretrain_DIY": "Pretrain.py", "imagenet": "Imagenet.py", "vqa": "VQA.py", "glue": "run_glue.py"}
+TASK_SCRIPTS = {"pretrain_DIY": "Pretrain.py", "imagenet": "Imagenet.py", "vqa": "VQA.py", "glue": "run_glue.py",
+                "refcoco_bbox": "Grounding_bbox.py"}
 DEFAULT_CONFIGS = {"pretrain_DIY": "configs/Pretrain_synthetic.yaml", "imagenet": "configs/Imagenet_synthetic.yaml",
-                   "vqa": "configs/VQA_synthetic.yaml", "glue": "configs/glue_synthetic.yaml"}
+                   "vqa": "configs/VQA_synthetic.yaml", "glue": "configs/glue_synthetic.yaml",
+                   "refcoco_bbox": "configs/Grounding_bbox_synthetic.yaml"}
 
 
 def get_dist(args, n_visible=None):
@@ -54,6 +60,10 @@ def task_command(args, n_visible=None):
         script_args = ["--config", args.config, "--output_dir", args.output_dir, "--seed", args.seed]
     elif args.task == "vqa":      # run.py:182-193: --bs is the global batch (VQA.py:134-135 divides it), --evaluate is passed on
         script_args = ["--config", args.config, "--output_dir", args.output_dir, "--bs", args.bs, "--seed", args.seed]
+        if args.evaluate:
+            script_args += ["--evaluate"]
+    elif args.task == "refcoco_bbox":   # run.py:196-207: --bs is the global batch (Grounding_bbox.py:105-106 divides it)
+        script_args = ["--config", args.config, "--output_dir", args.output_dir, "--bs", args.bs, "--seed", args.seed, "--load_bbox_pretrain"]
         if args.evaluate:
             script_args += ["--evaluate"]
     else:

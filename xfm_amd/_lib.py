@@ -13,7 +13,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # XFM_HIP_LIB: A/B a differently built library (kernel experiments); the default is the in-tree build.
 LIB_PATH = os.environ.get("XFM_HIP_LIB") or os.path.join(_HERE, "libxfm_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_void_p, c_int, c_long, c_float, c_u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_uint32
 
@@ -181,6 +181,7 @@ SIGNATURES = {
     "xfm_corr_rank": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "xfm_mse_fwd": (c_int, [c_void_p, c_long, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "xfm_mse_bwd": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "xfm_box_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p]),
     "xfm_mixup": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "xfm_mixup_target": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_long, c_void_p]),
     "xfm_region_pool_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

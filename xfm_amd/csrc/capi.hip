@@ -45,6 +45,7 @@ int xfm_cu_count() {
 #include "region.hip"
 #include "answer_rank.hip"
 #include "metrics.hip"
+#include "grounding.hip"
 #include "dp.hip"
 
 #define ST(s) ((hipStream_t)(s))
@@ -334,6 +335,10 @@ int xfm_mse_fwd(const void* pred, long stride, int pred_bf16, const float* targe
 }
 int xfm_mse_bwd(const void* pred, long stride, int pred_bf16, const float* target, const float* dloss, int B, float* dpred, void* stream) {
   return xfm_mse_bwd_impl(pred, stride, pred_bf16, target, dloss, B, dpred, ST(stream));
+}
+int xfm_box_eval(const float* coord, const int* ref_row, const float* ref_box, const float* ref_size, const int* ref_split, int n, int R,
+                 float* out, long out_offset, int64_t* counts, void* stream) {
+  return xfm_box_eval_impl(coord, ref_row, ref_box, ref_size, ref_split, n, R, out, out_offset, counts, ST(stream));
 }
 int xfm_mixup(float* x, int B, int C, int H, int W, const float* lam, const int* box, void* stream) {
   XFM_REQUIRE(x && lam && box, "mixup: null operand");

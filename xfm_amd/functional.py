@@ -993,6 +993,31 @@ def mse_bwd(pred, target, dloss):
     return dpred
 
 
+def box_eval(coord, ref_row, ref_box, ref_size, ref_split, counts, out=None, out_offset=0):
+    """xfm_box_eval: coord fp32 [n, 4] = (cx, cy, w, h) in [0, 1]; ref_row int32 [n] (or None = rows 0 .. n - 1) names each sample's row of
+    ref_box fp32 [R, 4] (x, y, w, h in pixels), ref_size fp32 [R, 2] (width, height), ref_split int32 [R] (0 val, 1 testA, 2 testB).
+    counts int64 [3, 2] += (#IoU >= 0.5, #samples) per split; out (fp32 [N, 5] device buffer, optional): row out_offset + i = (x, y, w, h
+    in pixels, IoU).  A row outside the tables: a NaN out row, counted nowhere."""
+    for t in (coord, ref_box, ref_size, ref_split, counts):
+        _dev(t)
+    n, R = coord.shape[0], ref_box.shape[0]
+    assert coord.dtype == F32 and coord.shape == (n, 4) and coord.is_contiguous()
+    assert ref_box.dtype == F32 and ref_box.shape == (R, 4) and ref_box.is_contiguous()
+    assert ref_size.dtype == F32 and ref_size.shape == (R, 2) and ref_size.is_contiguous()
+    assert ref_split.dtype == torch.int32 and ref_split.numel() == R and ref_split.is_contiguous()
+    assert counts.dtype == torch.int64 and counts.numel() == 6 and counts.is_contiguous()
+    if ref_row is not None:
+        _dev(ref_row)
+        assert ref_row.dtype == torch.int32 and ref_row.numel() == n and ref_row.is_contiguous()
+    if out is not None:
+        _dev(out)
+        assert out.dtype == F32 and out.dim() == 2 and out.shape[1] == 5 and out.is_contiguous()
+        assert out_offset < 0 or out_offset + n <= out.shape[0]
+    check(_lib.load().xfm_box_eval(coord.data_ptr(), _ptr(ref_row), ref_box.data_ptr(), ref_size.data_ptr(), ref_split.data_ptr(), n, R,
+                                   _ptr(out), int(out_offset), counts.data_ptr(), _stream()), "box_eval")
+    return counts
+
+
 def mixup_(x, lam, box):
     """In-place batch mix (xfm_mixup): x fp32 [B, C, H, W] contiguous, B even; row i against the original row B - 1 - i with lam fp32 [B]
     and box int32 [B, 4] = (yl, yh, xl, xh) on the device (lam 1: untouched; empty box: mixup; else CutMix inside the box) -> x."""

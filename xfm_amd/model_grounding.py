@@ -18,13 +18,17 @@ class XFMForGrounding(XFMBase):
             self._arena.bump()
         return msg
 
-    def forward(self, image, text_ids, text_atts, target_bbox=None):
+    def forward(self, image, text_ids, text_atts, target_bbox=None, fused=False):
+        """fused=True (HIP tensors): the two losses as one kernel each way (get_bbox_loss(fused=True): xfm_box_loss_fwd / bwd)."""
         image_embeds, _ = self.get_vision_embeds(image)
         text_embeds = self.get_text_embeds(text_ids, text_atts)
         output_coord = self.predict_bbox(image_embeds, text_ids, text_atts, text_embeds, is_pretrain=False)
         if target_bbox is None:
             return output_coord
-        loss_bbox, loss_giou = self.get_bbox_loss(output_coord, target_bbox)
+        if fused:
+            loss_bbox, loss_giou = self.get_bbox_loss(output_coord, target_bbox, fused=True)
+        else:
+            loss_bbox, loss_giou = self.get_bbox_loss(output_coord, target_bbox)
         return output_coord, loss_bbox, loss_giou
 
 

@@ -308,3 +308,48 @@ def glue_batch(batch_size, seed=1234, max_length=128, min_len=8, vocab=VOCAB, pa
     else:
         labels = torch.from_numpy(np.minimum((u * num_labels).astype(np.int64), num_labels - 1))
     return ids, atts, labels
+
+
+def _grounding_text(batch_size, seed, max_tokens, min_len, vocab):
+    """Expressions as Grounding_bbox.py:52 tokenizes them (`padding='longest'`): ids / atts int64 [B, T], T the longest row of the batch."""
+    b = pretrain_batch(batch_size, seed=seed, max_tokens=max_tokens, min_len=min(min_len, max_tokens), vocab=vocab, with_image=False)
+    atts = b["text_atts"]
+    T = int(atts.sum(1).max())
+    return b["text_ids"][:, :T].clone(), atts[:, :T].clone()
+
+
+def grounding_batch(batch_size, seed=1234, image_res=384, max_tokens=40, min_len=5, vocab=VOCAB):
+    """One training batch in the tuple layout of Grounding_bbox.py:50's loader, expressions as token ids: (image fp32 [B, 3, res, res],
+    (text_ids, text_atts) int64 [B, T], target_bbox fp32 [B, 4] = (cx, cy, w, h) in [0, 1], every box inside the image with w, h in
+    [0.1, 0.6])."""
+    image = gaussian(f"grounding.image.{seed}", (batch_size, 3, image_res, image_res))
+    ids, atts = _grounding_text(batch_size, seed, max_tokens, min_len, vocab)
+    u = uniform01("grounding.box", batch_size * 4, seed).reshape(batch_size, 4)
+    w, h = 0.1 + 0.5 * u[:, 2], 0.1 + 0.5 * u[:, 3]
+    cx, cy = w / 2 + u[:, 0] * (1.0 - w), h / 2 + u[:, 1] * (1.0 - h)
+    return image, (ids, atts), torch.from_numpy(np.stack([cx, cy, w, h], axis=1).astype(np.float32))
+
+
+def grounding_eval_batch(batch_size, seed=1234, image_res=384, max_tokens=40, min_len=5, first_ref_id=0, vocab=VOCAB):
+    """One test batch in the tuple layout of Grounding_bbox.py:81's loader: (image, (text_ids, text_atts), ref_ids int64 [B] =
+    first_ref_id + 0 .. B - 1)."""
+    image = gaussian(f"grounding.eval_image.{seed}", (batch_size, 3, image_res, image_res))
+    ids, atts = _grounding_text(batch_size, seed + 7919, max_tokens, min_len, vocab)
+    return image, (ids, atts), torch.arange(first_ref_id, first_ref_id + batch_size)
+
+
+def grounding_refs(num_refs, seed=1234, first_ref_id=0):
+    """The ground truth the grounding evaluation reads (refer.Refs / refToAnn / Imgs of dataset/utils.py:276-279) as three tables and an
+    index: ref_box fp32 [R, 4] = (x, y, w, h) in pixels, ref_size fp32 [R, 2] = (width, height), ref_split int32 [R] (0 val, 1 testA,
+    2 testB: row r is split r % 3, so all three occur from R = 3), ref_index = {ref_id: row}.  Every box is valid: x, y >= 0, w, h > 0,
+    inside its image; whole pixels, as the COCO annotations mostly are."""
+    from types import SimpleNamespace as NS
+    assert num_refs >= 3, "fewer than three refs cannot cover val, testA and testB"
+    u = uniform01("grounding.refs", num_refs * 6, seed).reshape(num_refs, 6)
+    W, H = np.floor(320 + 320 * u[:, 0]), np.floor(240 + 240 * u[:, 1])
+    w, h = np.floor(W * (0.1 + 0.5 * u[:, 2])) + 1, np.floor(H * (0.1 + 0.5 * u[:, 3])) + 1
+    x, y = np.floor(u[:, 4] * (W - w)), np.floor(u[:, 5] * (H - h))
+    return NS(ref_box=torch.from_numpy(np.stack([x, y, w, h], axis=1).astype(np.float32)),
+              ref_size=torch.from_numpy(np.stack([W, H], axis=1).astype(np.float32)),
+              ref_split=torch.from_numpy((np.arange(num_refs) % 3).astype(np.int32)),
+              ref_index={first_ref_id + r: r for r in range(num_refs)})
