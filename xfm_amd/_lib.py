@@ -117,6 +117,7 @@ class AdamWArgs(ctypes.Structure):
 
 
 MIM_SUMS_FLOATS = 3 + 3 * 512   # XFM_MIM_SUMS_FLOATS
+SUMSQ_WORKSPACE_FLOATS = 1024   # XFM_SUMSQ_WORKSPACE_FLOATS
 ANSWER_MAX_A, ANSWER_MAX_K = 8192, 1024   # XFM_ANSWER_MAX_A, XFM_ANSWER_MAX_K
 METRIC_MAX_L, CORR_MAX_N = 32, 8192       # XFM_METRIC_MAX_L, XFM_CORR_MAX_N
 

@@ -1043,7 +1043,7 @@ def mixup_target(labels, lam, num_classes, smoothing=0.0, ld=None):
 
 
 def sumsq(x, out):
-    ws = workspace(4096, x.device)  # XFM_SUMSQ_WORKSPACE_FLOATS block partials
+    ws = workspace(4 * _lib.SUMSQ_WORKSPACE_FLOATS, x.device)  # bytes: one fp32 block partial per grid block, at most XFM_SUMSQ_WORKSPACE_FLOATS
     check(_lib.load().xfm_sumsq(x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), _stream()), "sumsq")
 
 
