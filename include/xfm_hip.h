@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 16
+#define XFM_ABI_VERSION 17
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -581,6 +581,64 @@ int xfm_mse_bwd(const void* pred, long stride, int pred_bf16, const float* targe
  * XFM_E_ARG (nothing is launched): n < 1, R < 1, out_offset < 0, NULL coord / ref_box / ref_size / ref_split / counts. */
 int xfm_box_eval(const float* coord, const int* ref_row, const float* ref_box, const float* ref_size, const int* ref_split, int n, int R,
                  float* out, long out_offset, int64_t* counts, void* stream);
+
+/* ---- Incremental decoding (models/xbert.py:1368-1484 prepare_inputs_for_generation / _generate_no_beam_search; the cached branches of the
+ * attention at models/xroberta.py:224-262; ABI 17)
+ * xfm_decode_attn: attention of ONE new query token per batch row against a key/value cache, head_dim 64 (replaces, for a step with a past,
+ * xroberta.py:224-234 -- torch.cat of the past with the new key / value, or the re-projection of the encoder states -- and :240-262).
+ * Cache layout: token-major, element (b, s, h, d) at ptr[(b * cap + s) * rs + h * 64 + d], bf16, `cap` rows per entry; k_cache and v_cache
+ * share rs (the K | V projection of the encoder states, [sources * Sk, 2 D] with cap = Sk and rs = 2 D, is such a cache as it stands).
+ *   self mode (k_new != NULL):  row b of q / k_new / v_new ([B] rows of H * 64, row strides in elements, e.g. column slices of the QKV
+ *       GEMM output) is the new token; `pos` tokens are cached already (the same for every row).  The call writes k_new / v_new to cache
+ *       row pos and attends over rows 0 .. pos; Sk must be pos + 1, n_src must be B, kv_index NULL.  The workgroup that owns (b, h) is the
+ *       only one that touches that slice of the cache.
+ *   cross mode (k_new == NULL): the Sk keys of source kv_index[b] (NULL: b) are read, nothing is written; n_src = the number of sources.
+ *       A kv_index entry outside [0, n_src) reads nothing and yields a zero output row.
+ * key_keep (may be NULL): int32 rows of keep_ld >= Sk elements, one per source (self mode: per batch row); 0 adds -10000 to the score, as
+ * in xfm_attn_args.  score = scale q.k (+ -10000); softmax and P.V in fp32 (the probabilities are not rounded to bf16); o = bf16 rows
+ * [B, H * 64] with row stride o_rs.  q, k_new, v_new and the caches must start on 16 bytes, their row strides multiples of 8 elements.
+ * XFM_E_ARG (nothing is launched): pos + 1 > cap, Sk < 1, Sk > cap (cross), H * 64 > rs, a misaligned or NULL operand. */
+typedef struct {
+  const xfm_bf16* q; long q_rs;
+  const xfm_bf16* k_new; long k_new_rs;   /* NULL: cross mode */
+  const xfm_bf16* v_new; long v_new_rs;
+  xfm_bf16* k_cache; xfm_bf16* v_cache;   /* read only in cross mode */
+  long rs;                                /* row stride of both caches, elements */
+  xfm_bf16* o; long o_rs;
+  const int* key_keep; long keep_ld;
+  const int* kv_index; int n_src;
+  int B, H, cap, pos, Sk;
+  float scale;
+} xfm_decode_attn_args;
+int xfm_decode_attn(const xfm_decode_attn_args* a, void* stream);
+
+/* xfm_next_token: one launch per decoding step for xbert.py:1422-1462.  Per row b of the fp32 logits [B, ld] (V <= ld columns count) and
+ * of the id buffer ids int64 [B, ids_ld] with cur_len valid columns:
+ *   penalty != 1: every DISTINCT id of ids[b, :cur_len] inside [0, V) has its logit multiplied by `penalty` if negative, divided by it
+ *       otherwise (:1425-1432, where the reference walks a set); the logits themselves are not modified;
+ *   tok = argmax of the penalised row, the lowest column among equal maxima (:1444) -- or next_token[b] when next_token != NULL (:1441,
+ *       the draw itself stays with the caller);  lp = log_softmax(penalised row)[tok]                                     (:1447-1448)
+ *   u = unfinished[b];  ids[b, cur_len] = u ? tok : pad_id  (:1453-1454);  hist_unfinished[b, step] = u, hist_logprob[b, step] = lp
+ *       (:1449-1450; both [B, hist_ld]);  unfinished[b] = u && the written id is none of eos_ids[0 .. n_eos)                (:1461-1462);
+ *   *n_unfinished (may be NULL) += the number of rows still unfinished after the step (:1465, the host's early-exit check).
+ * No float atomics; every result is a plain store and the count an integer add per row: the same bits with and without
+ * XFM_DETERMINISTIC.  A pre-drawn token outside [0, V) gives lp = NaN and reads nothing.
+ * XFM_E_ARG (nothing is launched): cur_len outside [0, ids_ld), step outside [0, hist_ld), V > ld, V > XFM_NEXT_TOKEN_MAX_V,
+ * n_eos > XFM_NEXT_TOKEN_MAX_EOS, penalty <= 0, a NULL operand. */
+#define XFM_NEXT_TOKEN_MAX_V 131072
+#define XFM_NEXT_TOKEN_MAX_EOS 8
+typedef struct {
+  const float* logits; long ld; int V;
+  int64_t* ids; long ids_ld; int cur_len;
+  float penalty;
+  const int64_t* next_token;              /* NULL: greedy */
+  int* unfinished;                        /* [B], 1 / 0 */
+  int* hist_unfinished; float* hist_logprob; long hist_ld; int step;
+  int pad_id; int n_eos; int eos_ids[XFM_NEXT_TOKEN_MAX_EOS];
+  int* n_unfinished;
+  int B;
+} xfm_next_token_args;
+int xfm_next_token(const xfm_next_token_args* a, void* stream);
 
 /* ---- Device Mixup / CutMix (timm Mixup._mix_batch / _mix_elem and mixup_target as called at Imagenet.py:468-469; ABI 10) -------------
  * xfm_mixup: fp32 images [B, C, H, W], B even, mixed IN PLACE: row i against the original row j = B - 1 - i, with the per-row device

@@ -13,7 +13,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # XFM_HIP_LIB: A/B a differently built library (kernel experiments); the default is the in-tree build.
 LIB_PATH = os.environ.get("XFM_HIP_LIB") or os.path.join(_HERE, "libxfm_hip.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 c_void_p, c_int, c_long, c_float, c_u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_uint32
 
@@ -116,6 +116,23 @@ class AdamWArgs(ctypes.Structure):
                 ("clip_coef", c_void_p), ("n", c_long), ("zero_grad", c_int)]
 
 
+class DecodeAttnArgs(ctypes.Structure):   # xfm_decode_attn_args
+    _fields_ = [("q", c_void_p), ("q_rs", c_long), ("k_new", c_void_p), ("k_new_rs", c_long), ("v_new", c_void_p), ("v_new_rs", c_long),
+                ("k_cache", c_void_p), ("v_cache", c_void_p), ("rs", c_long), ("o", c_void_p), ("o_rs", c_long),
+                ("key_keep", c_void_p), ("keep_ld", c_long), ("kv_index", c_void_p), ("n_src", c_int),
+                ("B", c_int), ("H", c_int), ("cap", c_int), ("pos", c_int), ("Sk", c_int), ("scale", c_float)]
+
+
+NEXT_TOKEN_MAX_V, NEXT_TOKEN_MAX_EOS = 131072, 8   # XFM_NEXT_TOKEN_MAX_V, XFM_NEXT_TOKEN_MAX_EOS
+
+
+class NextTokenArgs(ctypes.Structure):   # xfm_next_token_args
+    _fields_ = [("logits", c_void_p), ("ld", c_long), ("V", c_int), ("ids", c_void_p), ("ids_ld", c_long), ("cur_len", c_int),
+                ("penalty", c_float), ("next_token", c_void_p), ("unfinished", c_void_p),
+                ("hist_unfinished", c_void_p), ("hist_logprob", c_void_p), ("hist_ld", c_long), ("step", c_int),
+                ("pad_id", c_int), ("n_eos", c_int), ("eos_ids", c_int * NEXT_TOKEN_MAX_EOS), ("n_unfinished", c_void_p), ("B", c_int)]
+
+
 MIM_SUMS_FLOATS = 3 + 3 * 512   # XFM_MIM_SUMS_FLOATS
 SUMSQ_WORKSPACE_FLOATS = 1024   # XFM_SUMSQ_WORKSPACE_FLOATS
 ANSWER_MAX_A, ANSWER_MAX_K = 8192, 1024   # XFM_ANSWER_MAX_A, XFM_ANSWER_MAX_K
@@ -183,6 +200,8 @@ SIGNATURES = {
     "xfm_mse_fwd": (c_int, [c_void_p, c_long, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "xfm_mse_bwd": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "xfm_box_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p]),
+    "xfm_decode_attn": (c_int, [ctypes.POINTER(DecodeAttnArgs), c_void_p]),
+    "xfm_next_token": (c_int, [ctypes.POINTER(NextTokenArgs), c_void_p]),
     "xfm_mixup": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "xfm_mixup_target": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_long, c_void_p]),
     "xfm_region_pool_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -46,6 +46,7 @@ int xfm_cu_count() {
 #include "answer_rank.hip"
 #include "metrics.hip"
 #include "grounding.hip"
+#include "decode.hip"
 #include "dp.hip"
 
 #define ST(s) ((hipStream_t)(s))
@@ -339,6 +340,14 @@ int xfm_mse_bwd(const void* pred, long stride, int pred_bf16, const float* targe
 int xfm_box_eval(const float* coord, const int* ref_row, const float* ref_box, const float* ref_size, const int* ref_split, int n, int R,
                  float* out, long out_offset, int64_t* counts, void* stream) {
   return xfm_box_eval_impl(coord, ref_row, ref_box, ref_size, ref_split, n, R, out, out_offset, counts, ST(stream));
+}
+int xfm_decode_attn(const xfm_decode_attn_args* a, void* stream) {
+  NOTNULL(a, "decode_attn");
+  return xfm_decode_attn_impl(*a, ST(stream));
+}
+int xfm_next_token(const xfm_next_token_args* a, void* stream) {
+  NOTNULL(a, "next_token");
+  return xfm_next_token_impl(*a, ST(stream));
 }
 int xfm_mixup(float* x, int B, int C, int H, int W, const float* lam, const int* box, void* stream) {
   XFM_REQUIRE(x && lam && box, "mixup: null operand");

@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AdamWArgs, AttnArgs, EmbedArgs, LnBwdArgs, LnFwdArgs, check
+from ._lib import AdamWArgs, AttnArgs, DecodeAttnArgs, EmbedArgs, LnBwdArgs, LnFwdArgs, NextTokenArgs, check
 
 BF16, F32 = torch.bfloat16, torch.float32
 EPI_BF16, EPI_F32, EPI_GELU, EPI_DGELU, EPI_F32_ACC = 0, 1, 2, 3, 4
@@ -1016,6 +1016,81 @@ def box_eval(coord, ref_row, ref_box, ref_size, ref_split, counts, out=None, out
     check(_lib.load().xfm_box_eval(coord.data_ptr(), _ptr(ref_row), ref_box.data_ptr(), ref_size.data_ptr(), ref_split.data_ptr(), n, R,
                                    _ptr(out), int(out_offset), counts.data_ptr(), _stream()), "box_eval")
     return counts
+
+
+def decode_attn(q, k_cache, v_cache, cap, H, scale, k_new=None, v_new=None, pos=0, Sk=None, key_keep=None, kv_index=None, out=None):
+    """xfm_decode_attn: one new query token per batch row against a token-major key/value cache (xroberta.py:224-262 with a past).
+    q [B, >= H*64] bf16 (a column slice of the QKV GEMM output will do); k_cache / v_cache: 2-D bf16 views [entries * cap, >= H*64] of the
+    cache, element (b, s, h, d) at row b * cap + s, column h * 64 + d, both with the same row stride.
+    Self mode (k_new / v_new given, [B, >= H*64] like q): writes them to cache row `pos` of every entry and attends over rows 0 .. pos.
+    Cross mode: reads the Sk keys of entry kv_index[b] (int32 [B]; None: b).  key_keep: int32 [entries, >= keys], 0 adds -10000.
+    Returns o bf16 [B, H*64]."""
+    for t in (q, k_cache, v_cache):
+        _dev(t)
+        assert t.dtype == BF16 and t.dim() == 2 and t.stride(1) == 1
+    B = q.shape[0]
+    assert k_cache.stride(0) == v_cache.stride(0) and k_cache.shape[0] == v_cache.shape[0] and k_cache.shape[0] % cap == 0
+    n_src = k_cache.shape[0] // cap
+    a = DecodeAttnArgs(q=q.data_ptr(), q_rs=q.stride(0), k_cache=k_cache.data_ptr(), v_cache=v_cache.data_ptr(), rs=k_cache.stride(0),
+                       n_src=n_src, B=B, H=H, cap=cap, pos=int(pos), scale=scale)
+    if k_new is not None:
+        for t in (k_new, v_new):
+            _dev(t)
+            assert t.dtype == BF16 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == B
+        assert kv_index is None and Sk in (None, pos + 1)
+        a.k_new, a.k_new_rs, a.v_new, a.v_new_rs, a.Sk = k_new.data_ptr(), k_new.stride(0), v_new.data_ptr(), v_new.stride(0), int(pos) + 1
+    else:
+        assert v_new is None and Sk is not None
+        a.Sk = int(Sk)
+    if key_keep is not None:
+        _dev(key_keep)
+        assert key_keep.dtype == torch.int32 and key_keep.dim() == 2 and key_keep.stride(1) == 1 and key_keep.shape[0] == n_src
+        assert key_keep.shape[1] >= a.Sk
+        a.key_keep, a.keep_ld = key_keep.data_ptr(), key_keep.stride(0)
+    if kv_index is not None:
+        _dev(kv_index)
+        assert kv_index.dtype == torch.int32 and kv_index.numel() == B and kv_index.is_contiguous()
+        a.kv_index = kv_index.data_ptr()
+    if out is None:
+        out = torch.empty((B, H * 64), dtype=BF16, device=q.device)
+    assert out.dtype == BF16 and out.shape == (B, H * 64) and out.stride(1) == 1
+    a.o, a.o_rs = out.data_ptr(), out.stride(0)
+    check(_lib.load().xfm_decode_attn(ctypes.byref(a), _stream()), "decode_attn")
+    return out
+
+
+def next_token(logits, V, ids, cur_len, unfinished, hist_unfinished, hist_logprob, step, pad_id, eos_ids, penalty=1.0, next_token=None,
+               n_unfinished=None):
+    """xfm_next_token: one decoding step's token choice (xbert.py:1422-1462) in one launch.  logits fp32 [B, ld >= V]; ids int64
+    [B, max_length] with cur_len valid columns (column cur_len is written); unfinished int32 [B] (updated); hist_unfinished int32 /
+    hist_logprob fp32 [B, steps] (column `step` is written); eos_ids: up to 8 ints; next_token int64 [B]: a pre-drawn token in place of
+    the argmax; n_unfinished int32 [1] (optional): += the rows still unfinished after the step."""
+    for t in (logits, ids, unfinished, hist_unfinished, hist_logprob):
+        _dev(t)
+    B = logits.shape[0]
+    assert logits.dtype == F32 and logits.dim() == 2 and logits.stride(1) == 1 and V <= logits.shape[1]
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[0] == B and ids.stride(1) == 1
+    assert unfinished.dtype == torch.int32 and unfinished.numel() == B and unfinished.is_contiguous()
+    assert hist_unfinished.dtype == torch.int32 and hist_logprob.dtype == F32 and hist_unfinished.shape == hist_logprob.shape
+    assert hist_unfinished.dim() == 2 and hist_unfinished.shape[0] == B and hist_unfinished.is_contiguous() and hist_logprob.is_contiguous()
+    eos = [int(e) for e in eos_ids]
+    assert len(eos) <= _lib.NEXT_TOKEN_MAX_EOS
+    a = NextTokenArgs(logits=logits.data_ptr(), ld=logits.stride(0), V=V, ids=ids.data_ptr(), ids_ld=ids.stride(0), cur_len=int(cur_len),
+                      penalty=float(penalty), unfinished=unfinished.data_ptr(), hist_unfinished=hist_unfinished.data_ptr(),
+                      hist_logprob=hist_logprob.data_ptr(), hist_ld=hist_unfinished.shape[1], step=int(step), pad_id=int(pad_id),
+                      n_eos=len(eos), B=B)
+    assert 0 <= int(cur_len) < ids.shape[1]
+    for i, e in enumerate(eos):
+        a.eos_ids[i] = e
+    if next_token is not None:
+        _dev(next_token)
+        assert next_token.dtype == torch.int64 and next_token.numel() == B and next_token.is_contiguous()
+        a.next_token = next_token.data_ptr()
+    if n_unfinished is not None:
+        _dev(n_unfinished)
+        assert n_unfinished.dtype == torch.int32 and n_unfinished.numel() == 1
+        a.n_unfinished = n_unfinished.data_ptr()
+    check(_lib.load().xfm_next_token(ctypes.byref(a), _stream()), "next_token")
 
 
 def mixup_(x, lam, box):

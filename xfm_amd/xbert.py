@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from .arena import LinearSlot, OwnsArena, ParamArena
 from .beit2 import _Affine
+from .decode import GenerationMixin
 from .ops import lm_head_ce, lm_head_logits
 from .xroberta import RobertaModel, _Emb, _Lin
 
@@ -139,12 +140,13 @@ class BertForMaskedLM(OwnsArena, nn.Module):
         return SimpleNamespace(loss=loss, logits=logits[:, :V].view(Bq, Tq, V), hidden_states=None, attentions=None)
 
 
-class BertLMHeadModel(OwnsArena, nn.Module):
+class BertLMHeadModel(GenerationMixin, OwnsArena, nn.Module):
     """Causal decoder with cross-attention to encoder states on the BERT-flavoured stack (xbert.py:1235-1347): what
     model_generation.py:54 builds as `text_decoder` for a bert-named text encoder.  Same fused stack and LM-head node as
     xroberta.RobertaForCausalLM; the state_dict keys are the reference's (`bert.*`, `cls.predictions.*`).  label_smoothing > 0
     (xbert.py:1346-1347, LabelSmoothSoftmaxCEV1 at :1190-1229; Captioning.yaml:28 sets 0.1) runs the label-form soft CE kernels inside
-    the same LM-head node.  Generation (beam search, past_key_values) is outside the hot-path scope, as for the RoBERTa decoder."""
+    the same LM-head node.  Generation (xfm_amd.decode): `use_cache` / `past_key_values`, `prepare_inputs_for_generation`, `_reorder_cache` and
+    `_generate_no_beam_search` (xbert.py:1368-1484), greedy and plain sampling; beam search and HF's generate() are not built."""
 
     def __init__(self, config, label_smoothing=0.0):
         super().__init__()
@@ -173,14 +175,13 @@ class BertLMHeadModel(OwnsArena, nn.Module):
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, head_mask=None,
                 inputs_embeds=None, encoder_hidden_states=None, encoder_attention_mask=None, labels=None, past_key_values=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, is_decoder=True,
-                reduction='mean', mode='multi_modal', return_logits=False, encoder_batch_index=None):
-        if past_key_values is not None or use_cache:
-            raise NotImplementedError("incremental decoding caches (generation) are outside the hot-path scope")
+                reduction='mean', mode='multi_modal', return_logits=False, encoder_batch_index=None, cache_capacity=None):
         # `encoder_batch_index` (extension, default None = the reference's call): row b cross-attends to encoder_hidden_states[index[b]], so
         # rows that share a source (rank_answer's k candidates per question) have its K/V projected once per layer (RobertaModel.forward)
         outputs = self.bert(input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, position_ids=position_ids,
                             head_mask=head_mask, inputs_embeds=inputs_embeds, encoder_hidden_states=encoder_hidden_states,
-                            encoder_attention_mask=encoder_attention_mask, is_decoder=is_decoder, mode=mode, encoder_batch_index=encoder_batch_index)
+                            encoder_attention_mask=encoder_attention_mask, is_decoder=is_decoder, mode=mode, encoder_batch_index=encoder_batch_index,
+                            past_key_values=past_key_values, use_cache=use_cache, cache_capacity=cache_capacity)
         seq = outputs.last_hidden_state
         head = self.cls.predictions
         V = self.config.vocab_size
@@ -189,11 +190,14 @@ class BertLMHeadModel(OwnsArena, nn.Module):
             logits = lm_head_logits(seq.reshape(-1, seq.shape[-1]), head).view(B, T, V)
             if return_logits:
                 return logits[:, :-1, :].contiguous()
-            return SimpleNamespace(loss=None, logits=logits, hidden_states=seq, past_key_values=None, attentions=None,
+            return SimpleNamespace(loss=None, logits=logits, hidden_states=seq, past_key_values=outputs.past_key_values, attentions=None,
                                    cross_attentions=None)
         shifted, lab = seq[:, :-1, :], labels[:, 1:]   # next-token prediction (xbert.py:1331-1333)
         loss, logits = lm_head_ce(shifted.reshape(-1, seq.shape[-1]), head, lab.reshape(-1), reduction, self.label_smoothing)
         if reduction == 'none':
             loss = loss.view(B, -1).sum(1)
-        return SimpleNamespace(loss=loss, logits=logits[:, :V].view(B, T - 1, V), hidden_states=seq, past_key_values=None,
+        return SimpleNamespace(loss=loss, logits=logits[:, :V].view(B, T - 1, V), hidden_states=seq, past_key_values=outputs.past_key_values,
                                attentions=None, cross_attentions=None)
+
+    def _generation_parts(self):
+        return self.bert, self.cls.predictions

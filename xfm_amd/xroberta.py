@@ -18,6 +18,7 @@ import torch.nn as nn
 from . import functional as Fx
 from .arena import LinearSlot, OwnsArena, ParamArena
 from .beit2 import _Affine, arena_note_grad, arena_note_use
+from .decode import GenerationMixin
 from .ops import grad_view, lm_head_ce, lm_head_logits
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -1120,7 +1121,7 @@ class RobertaModel(nn.Module):
                 inputs_embeds=None, encoder_embeds=None, encoder_hidden_states=None, encoder_attention_mask=None,
                 past_key_values=None, use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None,
                 is_decoder=False, mode='multi_modal', encoder_batch_index=None, grad_batch=None, pack=None, encoder_row_ranges=None,
-                output_rows=None):
+                output_rows=None, cache_capacity=None):
         """`encoder_batch_index` (extension, default None = reference behaviour): int tensor [B] mapping every text row to the
         row of `encoder_hidden_states` it attends to, so duplicated images are projected to K/V once per layer.
         `grad_batch` (extension): only the first grad_batch sequences of the batch propagate gradient through the layer stack
@@ -1132,9 +1133,19 @@ class RobertaModel(nn.Module):
         ragged problem per image on full 16-row query tiles instead of per-sequence tiles that are mostly padding.
         `output_rows` (extension, with `pack`): (rows int32 [S], start int32 [B], len int32 [B], max len) -- the caller reads only these
         token rows of the last layer (sequence b's are the block start[b] .. + len[b] of the S-row result): the last layer then runs
-        its queries / FFN / LayerNorms on them alone (_LastLayerRowsFn) and `last_hidden_state` is the [S, D] result."""
-        if any(v is not None for v in (token_type_ids, position_ids, head_mask, inputs_embeds, past_key_values)):
-            raise NotImplementedError("token_type_ids/position_ids/head_mask/inputs_embeds/past_key_values are not used on the XFM path")
+        its queries / FFN / LayerNorms on them alone (_LastLayerRowsFn) and `last_hidden_state` is the [S, D] result.
+        `use_cache` / `past_key_values` (the causal decoder in eval mode under torch.no_grad(); xfm_amd.decode): the prompt, then one token
+        per call, against a `decode.KVCache` returned as `.past_key_values`; a plain tuple of `[B, H, len, 64]` tensors is accepted and
+        copied (the slow path).  `cache_capacity` (extension): tokens per row a fresh cache holds, default the position-table size."""
+        if any(v is not None for v in (token_type_ids, position_ids, head_mask, inputs_embeds)):
+            raise NotImplementedError("token_type_ids/position_ids/head_mask/inputs_embeds are not used on the XFM path")
+        if use_cache or past_key_values is not None:
+            if any(v is not None for v in (encoder_embeds, grad_batch, pack, encoder_row_ranges, output_rows)):
+                raise NotImplementedError("use_cache / past_key_values take input_ids only (no encoder_embeds, grad_batch, pack, row ranges)")
+            from .decode import cached_forward
+            return cached_forward(self, input_ids, attention_mask=attention_mask, past_key_values=past_key_values,
+                                  encoder_hidden_states=encoder_hidden_states, encoder_attention_mask=encoder_attention_mask,
+                                  is_decoder=is_decoder, mode=mode, encoder_batch_index=encoder_batch_index, cache_capacity=cache_capacity)
         if isinstance(encoder_hidden_states, (list, tuple)):
             raise NotImplementedError("per-layer encoder_hidden_states lists (xroberta.py:435-444) are outside the hot-path scope")
         if self._arena is None:
@@ -1283,12 +1294,16 @@ class RobertaForMaskedLM(OwnsArena, nn.Module):
         return SimpleNamespace(loss=loss, logits=logits[:, :V].view(Bq, Tq, V), hidden_states=None, attentions=None)
 
 
-class RobertaForCausalLM(OwnsArena, nn.Module):
+class RobertaForCausalLM(GenerationMixin, OwnsArena, nn.Module):
     """Causal decoder with cross-attention to encoder states (the VQA answer decoder): mirrors models/xroberta.py:963-1153 --
     `roberta` + `lm_head`, causal self-attention mask, next-token shift, `reduction='none'` CE summed per sequence
     (:1107-1114).  `label_smoothing` is the keyword model_generation.py:275 passes to this class; the reference's own class does not
     take it (only its BERT sibling does, xbert.py:1240), so that call raises there.  Here it has the sibling's meaning
-    (LabelSmoothSoftmaxCEV1, xbert.py:1190-1229: 1 - s at the label, s / V elsewhere); 0 is the plain CE, kernel for kernel."""
+    (LabelSmoothSoftmaxCEV1, xbert.py:1190-1229: 1 - s at the label, s / V elsewhere); 0 is the plain CE, kernel for kernel.
+    Generation (xfm_amd.decode): `use_cache` / `past_key_values`, `prepare_inputs_for_generation` and `_reorder_cache` are the reference's
+    (xroberta.py:1130-1153).  `_generate_no_beam_search` exists in the reference only on the BERT sibling (xbert.py:1393-1484), yet
+    model_generation.py:353 calls it on this class -- an AttributeError there; here the class has the sibling's method, as with
+    `label_smoothing`.  Beam search and HF's generate() are not built."""
 
     def __init__(self, config, label_smoothing=0.0):
         super().__init__()
@@ -1314,14 +1329,13 @@ class RobertaForCausalLM(OwnsArena, nn.Module):
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, head_mask=None,
                 inputs_embeds=None, encoder_hidden_states=None, encoder_attention_mask=None, labels=None, past_key_values=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, is_decoder=True,
-                reduction='mean', mode='multi_modal', return_logits=False, encoder_batch_index=None):
-        if past_key_values is not None or use_cache:
-            raise NotImplementedError("incremental decoding caches (generation) are outside the hot-path scope")
+                reduction='mean', mode='multi_modal', return_logits=False, encoder_batch_index=None, cache_capacity=None):
         # `encoder_batch_index` (extension, default None = the reference's call): row b cross-attends to encoder_hidden_states[index[b]], so
         # rows that share a source (rank_answer's k candidates per question) have its K/V projected once per layer (RobertaModel.forward)
         outputs = self.roberta(input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, position_ids=position_ids,
                                head_mask=head_mask, inputs_embeds=inputs_embeds, encoder_hidden_states=encoder_hidden_states,
-                               encoder_attention_mask=encoder_attention_mask, is_decoder=is_decoder, mode=mode, encoder_batch_index=encoder_batch_index)
+                               encoder_attention_mask=encoder_attention_mask, is_decoder=is_decoder, mode=mode, encoder_batch_index=encoder_batch_index,
+                               past_key_values=past_key_values, use_cache=use_cache, cache_capacity=cache_capacity)
         seq = outputs.last_hidden_state
         V = self.config.vocab_size
         B, T = seq.shape[:2]
@@ -1329,11 +1343,14 @@ class RobertaForCausalLM(OwnsArena, nn.Module):
             logits = lm_head_logits(seq.reshape(-1, seq.shape[-1]), self.lm_head).view(B, T, V)
             if return_logits:
                 return logits[:, :-1, :].contiguous()
-            return SimpleNamespace(loss=None, logits=logits, hidden_states=seq, past_key_values=None, attentions=None,
+            return SimpleNamespace(loss=None, logits=logits, hidden_states=seq, past_key_values=outputs.past_key_values, attentions=None,
                                    cross_attentions=None)
         shifted, lab = seq[:, :-1, :], labels[:, 1:]
         loss, logits = lm_head_ce(shifted.reshape(-1, seq.shape[-1]), self.lm_head, lab.reshape(-1), reduction, self.label_smoothing)
         if reduction == 'none':
             loss = loss.view(B, -1).sum(1)
-        return SimpleNamespace(loss=loss, logits=logits[:, :V].view(B, T - 1, V), hidden_states=seq, past_key_values=None,
+        return SimpleNamespace(loss=loss, logits=logits[:, :V].view(B, T - 1, V), hidden_states=seq, past_key_values=outputs.past_key_values,
                                attentions=None, cross_attentions=None)
+
+    def _generation_parts(self):
+        return self.roberta, self.lm_head
