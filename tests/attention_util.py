@@ -57,7 +57,11 @@ on 16-byte boundaries, 4 rows before and 3 after); dO the same in a parent of it
 7.0-filled parents whose outside must keep its bits; dbias starts at 0.5 (so += is checked, and its columns [Sk, ld) must be
 bit-unchanged); stat_ld = 4 (Sq // 4 + 1), so lse and delta always have padding: the forward must leave it alone, and before the backward
 it is NaN in both (the backward must neither read nor write it); the given lse's whole parent must keep its bits; the bias-gradient workspace is exactly xfm_attn_bwd_workspace bytes
-inside a sentinel parent."""
+inside a sentinel parent.
+
+Two later sections of this file extend the same machinery: "the bias path" (xfm_bias_tile, xfm_relpos_gather and the three table-gradient
+forms: index restatements and the gradient bound) and "the dense routes" (no mask, no dropout, no packing: the route restatement
+dense_plan, dense_specs, the per-family counts and dense_fwd_ref / dense_bwd_ref); each has its own header."""
 from collections import namedtuple
 
 import torch
@@ -143,6 +147,8 @@ def make_case(sp):
     if sp.bias:
         ld = (Sk + 3) // 4 * 4 + (4 if Sk <= 256 else 0)       # past 256 keys the workspace route wants ld <= 64 chunks(Sk)
         c["bias"] = torch.zeros((H, Sq, ld))
+        if getattr(sp, "ld", 0):                                # a dense spec: its own row length, the padding never initialised
+            c["bias"] = torch.full((H, Sq, sp.ld), NAN)
         c["bias"][:, :, :Sk] = _randn((H, Sq, Sk), 5)
     return c
 
@@ -448,3 +454,431 @@ def ratio_line(sp, quantity, ratio):
 def max_norm_err(got, ref):
     """the measure of tests/test_hip_kernels.py: max |err| / max |ref|"""
     return float((got.double() - ref).abs().max() / ref.abs().max())
+
+
+# ---------------------------------------------------------------------------------------------------------------- the bias path
+# What feeds the dense kernels their bias (csrc/attention_aux.hip): the relative-position table is gathered into a dense [H, N, ld] bias
+# (xfm_relpos_gather), copied into the MFMA accumulator layout (xfm_bias_tile), and its gradient flows back into the table by one of three
+# forms (xfm_relpos_scatter: float atomics; xfm_relpos_scatter_sorted: one workgroup per entry over pre-sorted positions;
+# xfm_relpos_grid_grad: the structure of the standard grid index).  The two copies move values and are checked bit for bit against an
+# index restatement; the gradients are sums:
+#     dtable[e, h] = initial + sum over the n positions (i, j) with index[i, j] == e of ddense[h, i, j]
+#     bound        = (n + 1) u32 (|initial| + sum |ddense|)            [n additions of the terms and one onto the initial value, in
+#                                                                        whatever order: lanes, wave trees, atomics]
+def bias_tile_index(S):
+    """The accumulator layout of include/xfm_hip.h as indices: (q, k) int64 [T, T, 64, 4] of `tiled` (tile row a = query tile, column b =
+    key tile: query 16a + lr, key 16b + 4lg + r, lane = 16 lg + lr) and (k_t, q_t) int64 [T + 1, T, 64, 4] of `tiled_t` (row a = key tile:
+    key 16a + lr, query 16b + 4lg + r)."""
+    T = (S + 15) // 16
+    lane, r = torch.arange(64)[:, None], torch.arange(4)[None, :]
+    on_lane, on_reg = lane % 16, 4 * (lane // 16) + r                                    # [64, 1], [64, 4]
+
+    def grid(rows):
+        a, b = torch.arange(rows)[:, None, None, None], torch.arange(T)[None, :, None, None]
+        return (16 * a + on_lane).expand(rows, T, 64, 4), (16 * b + on_reg).expand(rows, T, 64, 4)
+
+    q, k = grid(T)
+    k_t, q_t = grid(T + 1)
+    return q, k, k_t, q_t
+
+
+def bias_tile_ref(bias, S, scale):
+    """bias fp32 [H, S, ld] -> (tiled [H, T, T, 64, 4], tiled_t [H, T + 1, T, 64, 4]) fp32, the exact bits xfm_bias_tile must write:
+    fl(bias fl(1 / scale)) with scale and its reciprocal in fp32, -1e30 where the key is past S, 0 where only the query is (the last
+    key-tile row of tiled_t lies wholly past S).  Reads nothing of bias's columns [S, ld)."""
+    inv = (torch.ones((), dtype=F32) / torch.tensor(scale, dtype=F32)).to(bias.device)
+    scaled = bias[:, :, :S] * inv
+    H = bias.shape[0]
+    neg, zero = torch.full((), -1.0e30, dtype=F32, device=bias.device), torch.zeros((), dtype=F32, device=bias.device)
+
+    def pick(q, k):
+        q, k = q.to(bias.device), k.to(bias.device)
+        val = scaled[:, q.clamp(max=S - 1), k.clamp(max=S - 1)]
+        return torch.where((k >= S).expand((H,) + k.shape), neg, torch.where((q >= S).expand((H,) + q.shape), zero, val))
+
+    q, k, k_t, q_t = bias_tile_index(S)
+    return pick(q, k), pick(q_t, k_t)
+
+
+def relpos_ref(table, index, H, N, ld):
+    """(dense, dense_t) fp32 [H, N, ld]: dense[h, i, j] = table[index[i, j], h], dense_t[h, i, j] = dense[h, j, i], columns [N, ld) zero"""
+    g = table[index.reshape(-1).long()].reshape(N, N, H).permute(2, 0, 1)
+    dense = torch.zeros((H, N, ld), dtype=F32, device=table.device)
+    dense_t = torch.zeros_like(dense)
+    dense[:, :, :N], dense_t[:, :, :N] = g, g.transpose(1, 2)
+    return dense, dense_t
+
+
+def table_grad_ref(ddense, index, entries, initial):
+    """ddense fp32 [H, N, >= N], index [N, N], initial fp32 [entries, H] -> (ref, b32) fp64 [entries, H] as the section's header says"""
+    H, N = ddense.shape[0], index.shape[0]
+    flat = index.reshape(-1).long().to(ddense.device)
+    terms = ddense[:, :, :N].double().reshape(H, N * N).t()                              # [N N, H]
+    z = torch.zeros((entries, H), dtype=F64, device=ddense.device)
+    count = torch.bincount(flat, minlength=entries).double().unsqueeze(1)
+    ref = initial.double() + z.clone().index_add_(0, flat, terms)
+    return ref, (count + 1) * U32 * (initial.double().abs() + z.index_add_(0, flat, terms.abs()))
+
+
+# ------------------------------------------------------------------------------------------------------------- the dense routes
+# No mask, no dropout, no packing: attn_fwd_vit_kernel (attention_vit.hip), the PLAIN = true general kernels and DQ_SUMS
+# (attention_general.hip), the short pair (attention_short.hip) and the three long kernels with dbias_reduce_kernel (attention_long.hip,
+# attention.hip).  The reference is fwd_ref / bwd_ref's (no mask, p = 0, the backward from the GIVEN fp32 lse); what differs per family
+# is where the roundings of a score fall.  With raw = scale q.k, mag = scale sum_d |q_d k_d|, b = the bias:
+#     e_s = u32 (66 (mag + A_b |b| + A_l |lse|) + (1 - A_b) |b| + 2 L (|raw| + |b| + |lse|))
+#   general    A_b = 0, A_l = 0, L = 0   fma(raw, scale, bias), __expf: the masked routes' count without the mask term
+#   vit        A_b = 1, A_l = 0, L = 0   the forward starts the MFMA accumulator from fl(bias fl(1 / scale)): the 64 additions carry |b| too
+#                                        (64 + that product + the fma = 66); p = exp2(fma(st, c2, fl(-max c2))), c2 = fl(scale log2 e): c2's
+#                                        own error and the fma's rounding are relative to |s - max| (e_p's 1.5 |s - rowmax|), the rounding
+#                                        of fl(-max c2) is common to the row and cancels in o; in lse it is u |max| <= u32 (|lse| + Sk)
+#   short_dq   A_b = 1, A_l = 0, L = 1   the same accumulator; p = exp2(fma(st, c2, fl(-lse log2 e))): c2's error is relative to |raw| + |b|,
+#                                        the lse product and its constant to |lse| -- four roundings of at most |raw| + |b| + |lse|: 2 u32
+#   short_dkv  A_b = 1, A_l = 1, L = 0   the accumulator starts from fl(fma(-lse, 1 / scale, bias / scale)): the additions carry |b| + |lse|;
+#                                        p = exp2(fl(st c2)), relative to |s - lse| (e_P's 1.5 |s - lse|)
+#   long       A_b = 0, A_l = 0, L = 1   raw from a zero accumulator; nb = fma(bias, log2 e, fl(-lse log2 e)) (the bias-gradient kernel:
+#                                        fl(bias log2 e) + fl(-lse log2 e)), p = exp2(fma(st, c2, nb)): the products with the constants,
+#                                        the constants themselves and the sum, each of at most |raw| + |b| + |lse|.  The tiled copy
+#                                        adds its own fl(bias fl(1 / scale)), within the same four.
+# The rest is the masked routes' (P, o, lse, dP, delta, dS, dq, dk, dv: header), with these differences:
+#     o, lse of the ViT forward     no online rescale: (Sk + 4) u32 in place of (Sk + 8 chunks) (the reciprocal, its product, log, the sum)
+#     delta from the output         where the kernel takes delta = dO . (O + O_lo) (short PRE, long and general with o_lo) the reference is that
+#                                   sum in fp64 from the bf16 O, O_lo it was given, b32 = C u32 sum_d |dO_d| (|O_d| + |Olo_d|), C = 66 for the
+#                                   fma chain of delta_from_out (64 terms, o + o_lo, the merge), 130 for the short kernel's packed dot
+#                                   products (128 products in fp32, the merges); dS is then formed from THAT delta
+#     o + o_lo                      |o + o_lo - ref| <= b32 + u16^2 (|ref| + b32): o_lo = bf16(v - bf16(v)) of the fp32 v, |v - bf16 v| <= u16 |v|
+#     dq, dk, dv                    dS (and P) cross LDS as bf16 in the short and long kernels as they enter the MFMA in the general ones:
+#                                   the same u16 |dS| term; dq takes the dQ side's e_s, dk / dv the dK/dV side's
+#     dbias                         sum_b e_dS + (B + F) u32 sum_b |dS| + F u32 |initial|: B additions of an entry's dS into the running sum
+#                                   (registers, nb at a time; planes) and F additions onto dbias -- F = slices for the short kernel
+#                                   (atomics or planes folded in order), ceil(B / nb) for DQ_SUMS, slices for the long kernels (1: in
+#                                   place), B for the general kernel's atomics
+# nb = 8 of DQ_SUMS needs ceil(blocks H ceil(B / 8) / 256) 8 <= the same with 4, i.e. more than 256 workgroups: not reachable at test
+# shapes (B = 33 gives 4), and XFM_ATTN_DBIAS_NB is read once per process.
+# The opt-in single pass (attn_bwd_vit3_kernel, XFM_ATTN_VIT_BWD = 3 / 4, 13-tile shapes, tiled bias): both sides are short_dkv's (the score
+# accumulator starts from fl(bias / scale - lse / scale), p = exp2(fl(sc c2))); delta = dO . O with the bf16 O (the fma chain: C = 66, O_lo = 0
+# in delta_out_ref); the dP accumulator starts from -delta, so its 64 additions carry |delta| too: e_dP += 66 u32 |delta|; the bias gradient
+# stays in registers across the items of a head: F = ceil(B / c) + 1 flushes at most (c = items per workgroup).  Mode 4 leaves the bias
+# gradient to attn_dbias_long_kernel on the delta the single pass wrote: the long family, F = its slices.
+#
+# Specs (H = 2 unless the case is about the heads).  Where the shapes first planned for a route and the code disagree the code wins:
+#     walking workgroup    vit_map is head-major flat by default: c = ceil(B H / 256) items per workgroup, so B = 129, H = 2 (258 items) gives
+#                          129 FULL workgroups; B = 87, H = 3 (261 items) gives 130 of two items and a last one of one, and workgroups
+#                          that straddle two heads (87 is odd).  Forward only.
+#     40 x 20              the short pair with Sk = 20: 2 key tiles, key-range waves 2 and 3 idle
+#     70 x 130, ld = 136   below cdiv(Sk, 16) 16 = 144: attn_short_dq_ok fails -> DQ_SUMS + the general dK/dV
+def cdiv(a, b):
+    return -(-a // b)
+
+
+RES_MAX = 4       # ATTN_RES_MAX
+FAM = {"general": (0, 0, 0), "vit": (1, 0, 0), "short_dq": (1, 0, 1), "short_dkv": (1, 1, 0), "long": (0, 0, 1)}
+C_DELTA_CHAIN, C_DELTA_DOT = 66, 130
+
+
+def attn_geom(S, max_nw=8):
+    tiles = cdiv(S, 16)
+    blocks = cdiv(tiles, min(tiles, max_nw))
+    return cdiv(tiles, blocks), blocks
+
+
+def attn_resident(S, nw):
+    return cdiv(S, 64) <= RES_MAX and nw >= 4
+
+
+def attn_vit_shape(Sq, Sk, ld):
+    return Sq == Sk and 64 < Sq <= 224 and (ld == 0 or (ld >= cdiv(Sk, 16) * 16 and ld % 4 == 0))
+
+
+def attn_vit3_shape(Sq, Sk, ld, mode, o_lo, tiled):
+    return mode != 0 and attn_vit_shape(Sq, Sk, ld) and cdiv(Sq, 16) == 13 and not o_lo and (ld == 0 or tiled)
+
+
+def attn_long_shape(Sq, Sk, ld, ldt, dbias):
+    return (Sk > 64 * RES_MAX and (ld == 0 or (ld % 4 == 0 and ld >= cdiv(Sk, 4) * 4)) and (ldt == 0 or (ldt % 4 == 0 and ldt >= cdiv(Sq, 4) * 4))
+            and (not dbias or (ld > 0 and ld <= cdiv(Sk, 128) * 128)))
+
+
+def attn_long_dkv_ok(ld, bias_t, tiled_square):
+    return ld == 0 or bias_t or tiled_square
+
+
+def attn_short_dq_ok(Sk, ld, dbias):
+    return Sk <= 64 * RES_MAX and (ld == 0 or ld >= cdiv(Sk, 16) * 16) and (not dbias or ld >= Sk)
+
+
+def attn_short_nb(B, H, rows, KT):
+    """-> (batch entries per slice, groups)"""
+    groups = cdiv(cdiv(rows, 16), KT)
+    z = max(1, min(B, 256 // (groups * H)))
+    return cdiv(B, z), groups
+
+
+def attn_short_dq_slices(B, H, Sq):
+    """-> (slices, groups, nb)"""
+    nb, groups = attn_short_nb(B, H, Sq, 3)
+    return cdiv(B, nb), groups, nb
+
+
+def attn_short_dq_np(Sk):
+    return 4 if Sk <= 128 else 7 if Sk <= 224 else 8
+
+
+def attn_short_planes_ok(Sk, ld):
+    return ld <= cdiv(Sk, 16) * 16
+
+
+def attn_dbias_sums_nb(B, H, blocks):
+    nb = 2 if B >= 8 else 1
+    if B >= 32:
+        c4, c8 = cdiv(blocks * H * cdiv(B, 4), 256) * 4, cdiv(blocks * H * cdiv(B, 8), 256) * 8
+        nb = 8 if c8 <= c4 else 4
+    return nb
+
+
+def dbias_long_slices(blocks, B, plane_bytes):
+    best, best_cost = 1, -1.0
+    for s in range(1, min(16, B) + 1):
+        cost = float(cdiv(blocks * s, 256)) * (2.0 * cdiv(B, s) + 3.0) + (s * float(plane_bytes) * 2.0 / 4.0e6 if s > 1 else 0.0)
+        if best_cost < 0 or cost < best_cost - 1e-9:
+            best, best_cost = s, cost
+    return best
+
+
+def attn_dbias_blocks_slices(B, H, Sq, Sk, ld):
+    return dbias_long_slices(cdiv(Sq, 128) * cdiv(Sk, 128) * H, B, H * Sq * ld * 4)
+
+
+def vit_map(B, H):
+    """the default (head-major flat) map -> (items per workgroup, workgroups, items of the last workgroup)"""
+    c = cdiv(B * H, 256)
+    grid = cdiv(B * H, c)
+    return c, grid, B * H - (grid - 1) * c
+
+
+Route = namedtuple("Route", "fwd dq dkv dbias nb slices planes")
+
+
+def dense_plan(sp, bias_t=True, tiled=False, o_lo=False, have_ws=True, vit_mode=0, pre=False, det=False):
+    """attn_bwd_plan (csrc/attention.hip) and the forward's choice (xfm_attn_fwd_impl) restated for a dense problem: which kernels a call
+    runs.  nb / slices: batch entries per workgroup and workgroup slices of the bias-gradient sum (0 where the route has none);
+    planes: what xfm_attn_bwd_workspace reports, in [H, Sq, bias_ld] fp32 planes."""
+    B, H, Sq, Sk, ld = sp.B, sp.H, sp.Sq, sp.Sk, sp.ld
+    has_bias = dbias = ld > 0
+    ldt = stat_ld(Sq) if has_bias and bias_t else 0
+    tiled = tiled and has_bias and Sq == Sk
+    if Sq <= 64 and Sk <= 64 and not has_bias and B >= 2:
+        fwd = "packed"
+    elif attn_vit_shape(Sq, Sk, ld):
+        fwd = "vit13" if cdiv(Sq, 16) == 13 else "vit_rt"
+    else:
+        fwd = "plain_res" if attn_resident(Sk, attn_geom(Sq)[0]) else "plain_stream"
+    ws_ok = have_ws and dbias and ld % 4 == 0 and ld <= cdiv(Sk, 64) * 64
+    dq = dkv = dbias_form = None
+    nb = slices = planes = 0
+    if attn_vit3_shape(Sq, Sk, ld, vit_mode, o_lo, tiled):
+        dq, dkv = "vit3", "vit3"
+        if dbias:
+            dbias_form = "blocks" if vit_mode == 4 and ld <= cdiv(Sk, 128) * 128 else "atomics"
+            # the single pass keeps sum_b dS in registers across the items of one head and flushes when the head changes: with c items a
+            # workgroup (head-major) a head's B entries lie in at most ceil(B / c) + 1 workgroups
+            nb = vit_map(B, H)[0]
+            slices = cdiv(B, nb) + 1
+    elif attn_long_shape(Sq, Sk, ld, ldt, dbias):
+        dq = "long"
+        dkv = "long" if attn_long_dkv_ok(ld, ldt > 0, tiled) else "general"
+        if dbias:
+            dbias_form = "blocks"
+    else:
+        short_ok = attn_short_dq_ok(Sk, ld, dbias)
+        nw, blocks = attn_geom(Sq)
+        if short_ok:
+            dq = "short_pre" if pre and o_lo else "short"
+            slices, _, nb = attn_short_dq_slices(B, H, Sq)
+            if dbias:
+                dbias_form = "short_planes" if ws_ok and attn_short_planes_ok(Sk, ld) and slices > 1 and det else "atomics"
+            if dbias_form == "short_planes":
+                planes = slices
+        elif dbias and attn_resident(Sk, nw):
+            dq, dbias_form = "sums", "sums"
+            nb = attn_dbias_sums_nb(B, H, blocks)
+            slices = cdiv(B, nb)
+        else:
+            dq = "general"
+            nb, slices = 1, B
+            if dbias:
+                dbias_form = "entry_ws" if ws_ok and Sk > 64 * RES_MAX else "atomics"
+            if dbias_form == "entry_ws":
+                planes = B
+        dkv = "short" if short_ok and Sq <= 224 else "general"
+    if dbias_form == "blocks":
+        slices = attn_dbias_blocks_slices(B, H, Sq, Sk, ld) if ws_ok else 1
+        nb = cdiv(B, slices)
+        planes = slices if slices > 1 else 0
+    if not dbias:
+        nb = slices = 0
+    return Route(fwd, dq, dkv, dbias_form, nb, slices, planes)
+
+
+# ld: bias row length (0: no bias); bwd: the backward runs too; want: the Route of the default call (transposed bias copy and a workspace
+# offered, no tiled copies, no o_lo, every knob at its default)
+DenseSpec = namedtuple("DenseSpec", "route B H Sq Sk U idx grouped mask causal p score bias name ld bwd want")
+
+
+def _dense(group, B, H, Sq, Sk, ld, want, score="randn", bwd=True):
+    name = (f"ld{ld}" if ld else "nobias") + ("" if score == "randn" else "+" + score)
+    return DenseSpec(group, B, H, Sq, Sk, B, None, False, None, False, 0.0, score, ld > 0, name, ld, bwd, Route(*want))
+
+
+def dense_specs():
+    S, A, G, L = "short", "atomics", "general", "long"
+    return [
+        # 1. the ViT forward with run-time tiles (backward: the short pair)
+        _dense("vit_rt", 2, 2, 65, 65, 0, ("vit_rt", S, S, None, 0, 0, 0)),
+        _dense("vit_rt", 2, 2, 65, 65, 80, ("vit_rt", S, S, A, 1, 2, 0)),
+        _dense("vit_rt", 2, 2, 130, 130, 144, ("vit_rt", S, S, A, 1, 2, 0)),
+        _dense("vit_rt", 2, 2, 224, 224, 224, ("vit_rt", S, S, A, 1, 2, 0)),
+        # 2. the 13-tile form
+        _dense("vit13", 2, 2, 197, 197, 0, ("vit13", S, S, None, 0, 0, 0)),
+        _dense("vit13", 2, 2, 197, 197, 208, ("vit13", S, S, A, 1, 2, 0)),
+        _dense("vit13", 2, 2, 197, 197, 208, ("vit13", S, S, A, 1, 2, 0), score="steep"),
+        _dense("vit13", 2, 2, 208, 208, 208, ("vit13", S, S, A, 1, 2, 0)),
+        # 3. walking workgroups: 261 items, two per workgroup, the last workgroup one; the second K / V image
+        _dense("vit_walk", 87, 3, 70, 70, 80, ("vit_rt", S, S, A, 3, 29, 0), bwd=False),
+        _dense("vit_walk", 87, 3, 197, 197, 208, ("vit13", S, S, A, 6, 15, 0), bwd=False),
+        # 4. the general plain forward
+        _dense("plain", 1, 2, 30, 197, 0, ("plain_stream", S, S, None, 0, 0, 0)),
+        _dense("plain", 2, 2, 30, 197, 0, ("plain_stream", S, S, None, 0, 0, 0)),
+        _dense("plain", 2, 2, 16, 16, 16, ("plain_stream", S, S, A, 1, 2, 0)),
+        _dense("plain", 2, 2, 40, 300, 0, ("plain_stream", L, L, None, 0, 0, 0), score="steep"),
+        _dense("plain", 2, 2, 130, 321, 0, ("plain_stream", L, L, None, 0, 0, 0)),
+        _dense("plain", 2, 2, 70, 130, 0, ("plain_res", S, S, None, 0, 0, 0)),
+        # 5. the short pair: Sk = 20 (two key-range waves idle), NP = 4 / 7 / 8, the longest query side of the short dK/dV, short dQ + general dK/dV
+        _dense("short", 2, 2, 40, 20, 32, ("plain_stream", S, S, A, 1, 2, 0)),
+        _dense("short", 2, 2, 100, 128, 128, ("plain_res", S, S, A, 1, 2, 0)),
+        _dense("short", 2, 2, 100, 256, 260, ("plain_res", S, S, A, 1, 2, 0)),
+        _dense("short", 2, 2, 250, 250, 256, ("plain_res", S, G, A, 1, 2, 0)),
+        _dense("short", 2, 2, 300, 256, 0, ("plain_res", S, G, None, 0, 0, 0)),
+        # 6. several entries per workgroup, a ragged last slice
+        _dense("short_nb", 11, 4, 250, 250, 256, ("plain_res", S, G, A, 2, 6, 0)),
+        # 7. more than one slice; with XFM_DETERMINISTIC=1 one plane per slice
+        _dense("short_slices", 9, 2, 40, 40, 48, ("plain_stream", S, S, A, 1, 9, 0)),
+        # 8. DQ_SUMS: nb = 1, 2 (ragged), 4 (ragged)
+        _dense("sums", 3, 2, 70, 130, 136, ("plain_res", "sums", G, "sums", 1, 3, 0)),
+        _dense("sums", 9, 2, 70, 130, 136, ("plain_res", "sums", G, "sums", 2, 5, 0)),
+        _dense("sums", 33, 2, 70, 130, 136, ("plain_res", "sums", G, "sums", 4, 9, 0)),
+        # 9. the long kernels (B = 2: the cost model of dbias_long_slices already takes two one-entry slices; 577 tokens take one, in place)
+        _dense("long", 2, 2, 40, 300, 304, ("plain_stream", L, L, "blocks", 1, 2, 2)),
+        _dense("long", 2, 2, 260, 260, 264, ("plain_stream", L, L, "blocks", 1, 2, 2)),
+        _dense("long", 2, 2, 300, 700, 704, ("plain_stream", L, L, "blocks", 1, 2, 2)),
+        _dense("long", 2, 2, 700, 300, 304, ("plain_stream", L, L, "blocks", 1, 2, 2)),
+        # 10. / 11. single-entry and two-entry slices of the bias-gradient kernel; 12. 577 tokens
+        _dense("long_slices", 3, 2, 260, 260, 264, ("plain_stream", L, L, "blocks", 1, 3, 3)),
+        _dense("long_slices", 17, 1, 260, 260, 264, ("plain_stream", L, L, "blocks", 2, 9, 9)),
+        _dense("long", 2, 2, 577, 577, 580, ("plain_stream", L, L, "blocks", 2, 1, 0)),
+    ]
+
+
+def dense_families(rt):
+    """(forward family, dQ-side family, dK/dV-side family) of a Route"""
+    side = {"short": "short_dq", "short_pre": "short_dq", "long": "long", "sums": "general", "general": "general", "vit3": "short_dkv"}
+    return ("vit" if rt.fwd.startswith("vit") else "general", side[rt.dq],
+            {"short": "short_dkv", "long": "long", "general": "general", "vit3": "short_dkv"}[rt.dkv])
+
+
+def dense_flushes(sp, rt):
+    """F of the dbias bound: additions onto dbias"""
+    return {"atomics": sp.B if rt.dq == "general" else rt.slices, "short_planes": rt.slices, "sums": rt.slices, "blocks": rt.slices,
+            "entry_ws": sp.B, None: 0}[rt.dbias]
+
+
+def dense_scores(c, fam, lse=None):
+    """(s, e_s) fp64 [B, H, Sq, Sk] for a dense case; lse fp64 [B, H, Sq] where the family's scores carry it"""
+    a_b, a_l, l2 = FAM[fam]
+    sp = c["sp"]
+    Q, K = _heads(c["q"]), _heads(c["k"])
+    raw = SCALE * (Q @ K.transpose(-1, -2))
+    mag = SCALE * (Q.abs() @ K.abs().transpose(-1, -2))
+    b = 0.0 * raw if c["bias"] is None else (c["bias"][:, :, :sp.Sk].double().unsqueeze(0) + 0.0 * raw)
+    lm = 0.0 if lse is None else lse.abs().unsqueeze(-1)
+    assert lse is not None or (a_l == 0 and l2 == 0)
+    e = C_K * (mag + a_b * b.abs() + a_l * lm) + (1 - a_b) * b.abs() + 2 * l2 * (raw.abs() + b.abs() + lm)
+    return raw + b, U32 * e
+
+
+def dense_fwd_ref(c, fam):
+    """-> {"o": (ref [B*Sq, H*64], b32), "lse": (ref [B*H, Sq], b32)}"""
+    sp = c["sp"]
+    s, e_s = dense_scores(c, fam)
+    lse = torch.logsumexp(s, -1)
+    P = torch.exp(s - lse.unsqueeze(-1))
+    e_p = e_s + U32 * (1.5 * (s - s.max(-1, keepdim=True).values).abs() + E_EXP)
+    V = _heads(c["v"])
+    o, mag = P @ V, P @ V.abs()
+    nsum = sp.Sk + (4 if fam == "vit" else 8 * chunks(sp.Sk))
+    lerr = (P * e_p).sum(-1)
+    b_o = (P * (U16 + e_p)) @ V.abs() + (o.abs() + mag) * (lerr + nsum * U32).unsqueeze(-1)
+    b_lse = lerr + U32 * (lse.abs() + nsum)
+    rows = lambda t: t.permute(0, 2, 1, 3).reshape(sp.B * sp.Sq, sp.H * 64)   # noqa: E731
+    return {"o": (rows(o), rows(b_o)), "lse": (lse.reshape(sp.B * sp.H, sp.Sq), b_lse.reshape(sp.B * sp.H, sp.Sq))}
+
+
+def check_o_lo(o, o_lo, ref, b32, what="o + o_lo"):
+    """o + o_lo against the fp64 o: the fp32 evaluation plus one bf16 rounding of the residual; returns the worst ratio"""
+    from gemm_strided_util import _check
+    return _check(o.double() + o_lo.double(), ref, b32 + U16 * U16 * (ref.abs() + b32), what)
+
+
+def delta_out_ref(c, o16, o_lo16, count):
+    """delta = dO . (O + O_lo) from the bf16 halves [B*Sq, H*64] the kernel is given -> (ref, b32) fp64 [B*H, Sq]"""
+    sp = c["sp"]
+    DO = c["do"].double().reshape(sp.B, sp.Sq, sp.H, 64)
+    O, L = (t.double().reshape(sp.B, sp.Sq, sp.H, 64) for t in (o16, o_lo16))
+    ref = (DO * (O + L)).sum(-1).permute(0, 2, 1)
+    mag = (DO.abs() * (O.abs() + L.abs())).sum(-1).permute(0, 2, 1)
+    return ref.reshape(sp.B * sp.H, sp.Sq), (count * U32 * mag).reshape(sp.B * sp.H, sp.Sq)
+
+
+def dense_bwd_ref(c, lse32, fam_q, fam_k, flushes, delta_given=None, fam_b=None, delta_in_acc=False):
+    """bwd_ref for a dense case whose dQ side (delta, dq, dbias) and dK/dV side (dk, dv) belong to the families fam_q / fam_k; flushes: F of
+    the header; delta_given: (ref, b32) [B*H, Sq] where the kernel takes delta from the forward's output; fam_b: the family of the kernel
+    that forms the bias gradient where that is not the dQ kernel; delta_in_acc: the dP accumulator starts from -delta (the single pass)."""
+    sp = c["sp"]
+    B, H, Sq, Sk = sp.B, sp.H, sp.Sq, sp.Sk
+    lse = lse32.double().reshape(B, H, Sq)
+    (s, e_sq), (_, e_sk) = dense_scores(c, fam_q, lse), dense_scores(c, fam_k, lse)
+    d = s - lse.unsqueeze(-1)
+    P = torch.exp(d)
+    e_Pq, e_Pk = (P * (e + U32 * (1.5 * d.abs() + E_EXP)) for e in (e_sq, e_sk))
+    Q, K, V, DO = _heads(c["q"]), _heads(c["k"]), _heads(c["v"]), _heads(c["do"])
+    dP = DO @ V.transpose(-1, -2)
+    e_dP = C_K * U32 * (DO.abs() @ V.abs().transpose(-1, -2))
+    if delta_given is None:
+        PdP = P * dP
+        delta = PdP.sum(-1)
+        e_delta = (e_Pq * dP.abs() + P * e_dP).sum(-1) + Sk * U32 * PdP.abs().sum(-1)
+    else:
+        delta, e_delta = (t.reshape(B, H, Sq) for t in delta_given)
+    dmd = dP - delta.unsqueeze(-1)
+    dS = P * dmd
+    if delta_in_acc:      # the 64 additions of dP carry |delta| as well
+        e_dP = e_dP + C_K * U32 * delta.abs().unsqueeze(-1)
+    e_dSq, e_dSk = (e * dmd.abs() + P * (e_dP + e_delta.unsqueeze(-1)) + 2 * U32 * dS.abs() for e in (e_Pq, e_Pk))
+    r16q, r16k = U16 * dS.abs() + e_dSq, U16 * dS.abs() + e_dSk
+    dq = SCALE * (dS @ K)
+    b_dq = SCALE * (r16q @ K.abs()) + (Sk + 2) * U32 * SCALE * (dS.abs() @ K.abs())
+    dk = SCALE * (dS.transpose(-1, -2) @ Q)
+    b_dk = SCALE * (r16k.transpose(-1, -2) @ Q.abs()) + (Sq + 2) * U32 * SCALE * (dS.abs().transpose(-1, -2) @ Q.abs())
+    dv = P.transpose(-1, -2) @ DO
+    b_dv = (U16 * P + e_Pk).transpose(-1, -2) @ DO.abs() + (Sq + 2) * U32 * (P.transpose(-1, -2) @ DO.abs())
+    rows = lambda t, S: t.permute(0, 2, 1, 3).reshape(B * S, H * 64)   # noqa: E731
+    out = {"delta": (delta.reshape(B * H, Sq), e_delta.reshape(B * H, Sq)), "dq": (rows(dq, Sq), rows(b_dq, Sq)),
+           "dk": (rows(dk, Sk), rows(b_dk, Sk)), "dv": (rows(dv, Sk), rows(b_dv, Sk))}
+    if c["bias"] is not None:
+        ref = DBIAS_INIT + dS.sum(0)
+        e_dSb = e_dSq
+        if fam_b is not None:
+            e_Pb = P * (dense_scores(c, fam_b, lse)[1] + U32 * (1.5 * d.abs() + E_EXP))
+            e_dSb = e_Pb * dmd.abs() + P * (e_dP + e_delta.unsqueeze(-1)) + 2 * U32 * dS.abs()
+        b = e_dSb.sum(0) + (B + flushes) * U32 * dS.abs().sum(0) + flushes * U32 * DBIAS_INIT
+        out["dbias"] = (ref.reshape(H * Sq, Sk), b.reshape(H * Sq, Sk))
+    return out
