@@ -68,6 +68,17 @@ def gelu_grad64(u):
     return _phi(u) + u * _pdf(u)
 
 
+def gelu_parts32(x, c3=0.7478556):
+    """common.h's gelu_parts in fp32: Abramowitz-Stegun 7.1.25 -> (cdf, pdf); c3: the polynomial's leading coefficient (the host tests plant a
+    wrong one)"""
+    ax = x.abs()
+    t = 1.0 / (0.33267 * ax + 1.0)
+    e = torch.exp2(-0.72134752 * x * x)
+    poly = t * (t * (t * c3 - 0.0958798) + 0.3480242)
+    erf_abs = 1.0 - poly * e
+    return torch.copysign(torch.full_like(x, 0.5), x) * erf_abs + 0.5, 0.39894228040143267 * e
+
+
 # ------------------------------------------------------------------------------------------------------------- poisoned buffers
 def poisoned_in(t, device):
     """an input as a whole-row range of a NaN-filled parent: 4 rows before and 3 after a matrix, 8 elements around a vector (offsets that

@@ -102,6 +102,7 @@ def _nt_contiguous(M, N, K, hint):
 
 NT_SMALL_HINTS = [1, 2, 3, 4, 7, 8, 0]
 NT_CASES = ([(300, 200, 128, h) for h in NT_SMALL_HINTS] + [(5, 3, 64, h) for h in NT_SMALL_HINTS]
+            + [(300, 203, 64, h) for h in NT_SMALL_HINTS]   # ragged N on the small tiles: full chunks, then a partial one that is not chunk 0
             + [(16400, 1001, 64, 5),    # 260 tiles of 256 x 256 > CUs: the persistent form, ragged M and N
                (300, 256, 128, 5),      # one workgroup per tile
                (21800, 520, 64, 0)])    # tail split: the second call offsets A, C and aux by rows_a * ld

@@ -4,7 +4,8 @@ Tolerances: inputs are bf16 (exact products), accumulation fp32; outputs that ar
 Elementwise fp64 bounds for the LayerNorm and cross-entropy kernels live in tests/test_hip_layernorm_bounds.py and tests/test_hip_ce_bounds.py,
 those for the attention routes with a key mask, a causal mask or dropout in tests/test_hip_attention_bounds.py.
 The embedding kernels have theirs in tests/test_hip_embedding_bounds.py, the row moves, the ViT input kernels and the MIM loss in
-tests/test_hip_token_rows_bounds.py."""
+tests/test_hip_token_rows_bounds.py.
+The GELU / dGELU epilogues of xfm_gemm_nt have theirs, on every tile configuration, in tests/test_hip_gemm_epilogue_bounds.py."""
 import math
 
 import pytest

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import rowwise_util as R
-from rowwise_util import BF16, F32, U32
+from rowwise_util import BF16, F32, U32, gelu_parts32
 
 CPU_F32_MAX, CPU_BF16_MAX = 0.75, 1.0
 
@@ -32,16 +32,6 @@ def lane_sum(t):
         n //= 2
         acc = acc[:, :n] + acc[:, n:2 * n]
     return acc[:, 0]
-
-
-def gelu_parts32(x):
-    """common.h's gelu_parts in fp32: Abramowitz-Stegun 7.1.25"""
-    ax = x.abs()
-    t = 1.0 / (0.33267 * ax + 1.0)
-    e = torch.exp2(-0.72134752 * x * x)
-    poly = t * (t * (t * 0.7478556 - 0.0958798) + 0.3480242)
-    erf_abs = 1.0 - poly * e
-    return torch.copysign(torch.full_like(x, 0.5), x) * erf_abs + 0.5, 0.39894228040143267 * e
 
 
 def emul_ln_fwd(v, w, b, eps, gelu=False):
