@@ -218,8 +218,11 @@ typedef struct {
      [1, Sq]) of q / o / dout / dq, its keys rows k_start[b] .. + k_len[b] of k / v / dk / dv; NULL = dense b * S rows.  Sq / Sk
      stay the padded lengths (grids, statistics [B,H,stat_ld], dropout counters).  Keys past k_len get probability exactly 0,
      what the reference's additive -10000 mask yields in fp32 for a prefix-masked batch (xroberta.py:751-807), so no key_keep
-     is needed.  Rows of o / dq / dk / dv outside every sequence are not written.  No bias, no kv_index in this mode; in grouped
-     mode only the query side may be packed. */
+     is needed.  Rows of o / o_lo / dq / dk / dv outside every sequence are not written, and neither are columns [q_len[b], stat_ld)
+     of entry b's rows of lse / delta: the forward stores no statistic there, and whatever the backward finds there (it may load
+     those columns) reaches no output.  The causal mask and key_keep apply on an entry's local indices (key_keep rows keep the
+     padded stride Sk).  No bias, no kv_index in this mode; in grouped mode only the query side may be packed: k_start / k_len
+     with grp_start is rejected (XFM_E_ARG), the sources' keys are the dense rows g * Sk .. + Sk. */
   const int* q_start; const int* q_len; const int* k_start; const int* k_len;
   /* xfm_attn_bwd only: 0 = both kernels; 1 = the dQ kernel alone (writes dq and the row statistics `delta`); 2 = the dK/dV kernel
      alone (reads the `delta` a phase-1 call left) -- lets a caller put dK/dV, which in cross-attention only feed weight gradients,

@@ -59,9 +59,10 @@ bit-unchanged); stat_ld = 4 (Sq // 4 + 1), so lse and delta always have padding:
 it is NaN in both (the backward must neither read nor write it); the given lse's whole parent must keep its bits; the bias-gradient workspace is exactly xfm_attn_bwd_workspace bytes
 inside a sentinel parent.
 
-Two later sections of this file extend the same machinery: "the bias path" (xfm_bias_tile, xfm_relpos_gather and the three table-gradient
-forms: index restatements and the gradient bound) and "the dense routes" (no mask, no dropout, no packing: the route restatement
-dense_plan, dense_specs, the per-family counts and dense_fwd_ref / dense_bwd_ref); each has its own header."""
+Three later sections of this file extend the same machinery: "the bias path" (xfm_bias_tile, xfm_relpos_gather and the three table-gradient
+forms: index restatements and the gradient bound), "the dense routes" (no mask, no dropout, no packing: the route restatement
+dense_plan, dense_specs, the per-family counts and dense_fwd_ref / dense_bwd_ref) and "ragged rows" (q_start / q_len / k_start / k_len,
+o_lo on masked problems: the layout, the per-entry reference, RaggedBuffers, ragged_specs); each has its own header."""
 from collections import namedtuple
 
 import torch
@@ -296,9 +297,12 @@ def fwd_ref(c, M=None):
     return {"o": (rows(o), rows(b_o)), "lse": (lse.reshape(sp.B * sp.H, sp.Sq), b_lse.reshape(sp.B * sp.H, sp.Sq))}
 
 
-def bwd_ref(c, lse32, M=None):
+def bwd_ref(c, lse32, M=None, delta_given=None, nq=None):
     """lse32: the fp32 [B*H, Sq] statistics handed to the kernels.  -> (ref, b32) pairs: delta [B*H, Sq], dq [B*Sq, H*64], dk / dv
-    [N*Sk, H*64] (N = B per query row for the general kernels, = U folded per source for the grouped ones), dbias [H*Sq, Sk] (with a bias)."""
+    [N*Sk, H*64] (N = B per query row for the general kernels, = U folded per source for the grouped ones), dbias [H*Sq, Sk] (with a bias).
+    delta_given: (ref, b32) [B*H, Sq] where the kernel takes delta from the forward's output (delta_out_ref), dS is then formed from that
+    delta as in dense_bwd_ref; nq: the additions of a dk / dv element where the caller knows better (the ragged section: a source's live
+    query rows + 2)."""
     sp = c["sp"]
     B, H, Sq, Sk = sp.B, sp.H, sp.Sq, sp.Sk
     lse = lse32.double().reshape(B, H, Sq)
@@ -313,6 +317,8 @@ def bwd_ref(c, lse32, M=None):
     PdP = P * dP
     delta = PdP.sum(-1)
     e_delta = (e_P * dP.abs() + P * e_dP).sum(-1) + Sk * U32 * PdP.abs().sum(-1)
+    if delta_given is not None:
+        delta, e_delta = (t.reshape(B, H, Sq) for t in delta_given)
     dmd = dP - delta.unsqueeze(-1)
     dS = P * dmd
     e_dS = e_P * dmd.abs() + P * (e_dP + e_delta.unsqueeze(-1)) + 2 * U32 * dS.abs()
@@ -320,9 +326,8 @@ def bwd_ref(c, lse32, M=None):
     dq = SCALE * (dS @ K)
     b_dq = SCALE * (r16 @ K.abs()) + (Sk + 2) * U32 * SCALE * (dS.abs() @ K.abs())
     W = P * F
-    nq = Sq + 2
-    if sp.grouped:
-        nq = Sq * int(torch.bincount(c["idx"], minlength=sp.U).max()) + 2
+    if nq is None:
+        nq = Sq * int(torch.bincount(c["idx"], minlength=sp.U).max()) + 2 if sp.grouped else Sq + 2
     dk = SCALE * (dS.transpose(-1, -2) @ Q)
     b_dk = SCALE * (r16.transpose(-1, -2) @ Q.abs()) + nq * U32 * SCALE * (dS.abs().transpose(-1, -2) @ Q.abs())
     dv = W.transpose(-1, -2) @ DO
@@ -882,3 +887,283 @@ def dense_bwd_ref(c, lse32, fam_q, fam_k, flushes, delta_given=None, fam_b=None,
         b = e_dSb.sum(0) + (B + flushes) * U32 * dS.abs().sum(0) + flushes * U32 * DBIAS_INIT
         out["dbias"] = (ref.reshape(H * Sq, Sk), b.reshape(H * Sq, Sk))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ ragged rows
+# Unpadded token rows (q_start / q_len / k_start / k_len of xfm_attn_args), the way xfm_rlayer_fwd / bwd call the kernels
+# (csrc/encoder.hip): self-attention with both pairs (q_start == k_start), range-mode cross-attention with the query pair and dense
+# keys (B = sources), grouped cross-attention with the query pair; and o_lo on masked / dropped / grouped problems, ragged or not.
+# Ragged rows never leave the general kernels (attention_general.hip; the packed forward xattn_fwd_kernel<true, ...> up to 64 x 64 with
+# B >= 2) and the grouped ones: attn_vit_shape, attn_long_shape and attn_short_dq_ok all require q_start == k_start == NULL.
+#
+# Reference.  The semantics are EXCLUSION: entry b is fwd_ref / bwd_ref on the sliced operands, queries [0, q_len[b]), keys [0, k_len[b])
+# of its source (entry_case), so every Sk and Sq of the header's counts -- (Sk + 8 chunks), Sk + 2, Sq + 2 -- is the entry's own length,
+# key_keep and the causal mask apply on local indices, and the dropout mask is the [:q_len, :k_len] corner of the padded [B, H, Sq, Sk]
+# array (the counters stay laid out for the padded Sq: drop_key in attention_common.h).  A key past k_len gets EXCL_NEG = -1e30 in
+# score_masked, exp(-1e30 - m) is exactly 0: no rounding to count, and no -10000 -- a row whose live keys are all masked is a softmax over
+# its LIVE keys alone.  Grouped dk / dv are the sum over the source's entries of the entries' own references; a source's element is the sum
+# of sum(q_len of its entries) products, so the addition count of every entry's term is that sum + 2 (bwd_ref's nq), for a bound of
+# (sum q_len + 2) u32 sum |terms| on the whole.  No constant is new.
+# delta from the output (o_lo given): attn_bwd_dq_kernel, xattn_dq_kernel and xattn_dq_stream_kernel all call delta_from_out
+# (attention_common.h), the fma chain counted at C_DELTA_CHAIN = 66 in the dense section; the reference is delta_out_ref on the entry's
+# rows of the bf16 o / o_lo the kernel was given, and dS, dq, dk, dv are formed from THAT delta (bwd_ref's delta_given).  Without o_lo
+# delta stays sum_j P dP of the dropped dP.
+# Statistics.  attn_fwd_kernel (`if (!wave_active || qi >= sq) return`), xattn_fwd_kernel (`if (qi < sq)`), xattn_fwd_stream_kernel
+# (`ok && qi < sq`) store lse only for qi < q_len[b], the three dQ kernels store delta under `qvalid`: columns [q_len[b], stat_ld) of
+# entry b's rows of lse / delta keep their bits on every route.  The dK/dV kernels LOAD them (16-byte loads up to the padded Sq) and
+# select them away, so the given lse and the delta buffer hold NaN there before the backward.
+#
+# Layout (ragged_layout, "shuffled"): entry b's live rows sit at start[b] of the row buffer; entries are stored in the order 1, 0, 2,
+# 3, ... (starts not monotone in b) with two slack rows in front and 1 + b % 3 behind each; in self-attention q, k, v are column slices of
+# one parent and q_start == k_start, an entry taking max(q_len, k_len) rows.  Slack rows of the inputs are NaN; slack rows of o, o_lo, dq,
+# dk, dv are the sentinel inside the sentinel parents and must keep their bits (RaggedBuffers.check_outside).  A dense side is b * S rows.
+RaggedSpec = namedtuple("RaggedSpec", Spec._fields + ("q_len", "k_len", "layout"))
+Layout = namedtuple("Layout", "q_start q_len q_rows k_start k_len k_rows")
+
+
+def _place(lens):
+    order = ([1, 0] + list(range(2, len(lens)))) if len(lens) > 1 else [0]
+    start, row = [0] * len(lens), 2
+    for b in order:
+        start[b] = row
+        row += lens[b] + 1 + b % 3
+    return tuple(start), row
+
+
+def ragged_layout(sp):
+    """Where the rows of every entry sit: (q_start, q_len, q_rows, k_start, k_len, k_rows); the key side has U entries.  dk / dv rows
+    follow the key side (per query entry in self-attention and range mode, where U == B; per source when grouped)."""
+    dense_q = (tuple(b * sp.Sq for b in range(sp.B)), (sp.Sq,) * sp.B, sp.B * sp.Sq)
+    dense_k = (tuple(u * sp.Sk for u in range(sp.U)), (sp.Sk,) * sp.U, sp.U * sp.Sk)
+    if sp.q_len is None:
+        assert sp.k_len is None
+        return Layout(*dense_q, *dense_k)
+    assert sp.layout == "shuffled" and len(sp.q_len) == sp.B and all(1 <= n <= sp.Sq for n in sp.q_len)
+    if sp.k_len is None:
+        start, rows = _place(sp.q_len)
+        return Layout(start, tuple(sp.q_len), rows, *dense_k)
+    assert sp.U == sp.B and sp.idx is None and len(sp.k_len) == sp.B and all(1 <= n <= sp.Sk for n in sp.k_len)
+    start, rows = _place([max(a, b) for a, b in zip(sp.q_len, sp.k_len)])
+    return Layout(start, tuple(sp.q_len), rows, start, tuple(sp.k_len), rows)
+
+
+def ragged_live(sp, device="cpu"):
+    """bool masks of what the kernels own: "q" [q_rows], "k" [k_rows] (rows of a sequence), "stat" [B*H, Sq] (columns below q_len[b])"""
+    lay = ragged_layout(sp)
+    q, k = torch.zeros(lay.q_rows, dtype=torch.bool), torch.zeros(lay.k_rows, dtype=torch.bool)
+    for s, n in zip(lay.q_start, lay.q_len):
+        q[s:s + n] = True
+    for s, n in zip(lay.k_start, lay.k_len):
+        k[s:s + n] = True
+    stat = (torch.arange(sp.Sq)[None, :] < torch.tensor(lay.q_len)[:, None]).repeat_interleave(sp.H, 0)
+    return {"q": q.to(device), "k": k.to(device), "stat": stat.to(device)}
+
+
+def make_ragged_case(sp):
+    """make_case on the padded shape (so a ragged case and its padded twin share every operand); steep: the planted key 8 e also at every
+    source's last kept LIVE key, so the running maximum of a shorter entry ends in ITS last chunk too."""
+    c = make_case(sp)
+    if sp.score == "steep" and sp.k_len is not None:
+        for u, n in enumerate(sp.k_len):
+            kept = torch.ones(n, dtype=torch.bool) if c["keep"] is None else c["keep"][u, :n] != 0
+            if bool(kept.any()):      # (holes mask key 0 of the even sources: an entry of one key has no kept key, and nothing planted)
+                c["k"][u, int(kept.nonzero().max())] = 1.0
+    return c
+
+
+def entry_case(c, b, M=None, q_len=None, k_len=None):
+    """(case, mask) of entry b alone on its sliced operands: B = U = 1, Sq = q_len[b], Sk = k_len of its source (q_len / k_len: other
+    lengths, for a planted fault)"""
+    sp = c["sp"]
+    lay = ragged_layout(sp)
+    src = int(c["idx"][b])
+    ql = lay.q_len[b] if q_len is None else q_len
+    kl = lay.k_len[src] if k_len is None else k_len
+    spb = Spec(sp.route, 1, sp.H, ql, kl, 1, None, sp.grouped, sp.mask, sp.causal, sp.p, sp.score, False, sp.name)
+    cb = {"sp": spb, "q": c["q"][b:b + 1, :ql], "do": c["do"][b:b + 1, :ql], "k": c["k"][src:src + 1, :kl], "v": c["v"][src:src + 1, :kl],
+          "bias": None, "keep": None if c["keep"] is None else c["keep"][src:src + 1, :kl],
+          "idx": torch.zeros(1, dtype=torch.int64, device=c["q"].device)}
+    return cb, (None if M is None else M[b:b + 1, :, :ql, :kl])
+
+
+def _stat_rows(t, sp, b, ql):
+    """entry b's [H, ql] corner of a [B*H, Sq] statistic"""
+    return t.reshape(sp.B, sp.H, sp.Sq)[b, :, :ql]
+
+
+def ragged_fwd_ref(c, M=None):
+    """-> {"o": (ref, b32) [q_rows, H*64] in the buffer's row layout, "lse": (ref, b32) [B*H, Sq]}; compare where ragged_live says so
+    (slack rows and dead columns hold 0 here)"""
+    sp = c["sp"]
+    lay = ragged_layout(sp)
+    dev = c["q"].device
+    o = [torch.zeros((lay.q_rows, sp.H * 64), dtype=F64, device=dev) for _ in range(2)]
+    lse = [torch.zeros((sp.B * sp.H, sp.Sq), dtype=F64, device=dev) for _ in range(2)]
+    for b in range(sp.B):
+        cb, Mb = entry_case(c, b, M)
+        fr = fwd_ref(cb, Mb)
+        s, n = lay.q_start[b], lay.q_len[b]
+        for i in range(2):
+            o[i][s:s + n] = fr["o"][i]
+            _stat_rows(lse[i], sp, b, n).copy_(fr["lse"][i])
+    return {"o": tuple(o), "lse": tuple(lse)}
+
+
+def ragged_lse32(fr, sp):
+    """the statistics handed to the backward: fp32 of the reference's lse, NaN in the dead columns"""
+    return torch.where(ragged_live(sp, fr["lse"][0].device)["stat"], fr["lse"][0].float(), torch.full((), NAN, device=fr["lse"][0].device))
+
+
+def ragged_bwd_ref(c, lse32, M=None, o16=None, o_lo16=None):
+    """-> (ref, b32) pairs: delta [B*H, Sq], dq [q_rows, H*64], dk / dv [k_rows, H*64] in the buffers' row layouts (grouped: summed per
+    source).  o16, o_lo16 [q_rows, H*64]: the bf16 halves the kernel is given; delta is then delta_out_ref's (C_DELTA_CHAIN)."""
+    sp = c["sp"]
+    lay = ragged_layout(sp)
+    dev = c["q"].device
+    D = sp.H * 64
+    out = {"delta": [torch.zeros((sp.B * sp.H, sp.Sq), dtype=F64, device=dev) for _ in range(2)],
+           "dq": [torch.zeros((lay.q_rows, D), dtype=F64, device=dev) for _ in range(2)],
+           "dk": [torch.zeros((lay.k_rows, D), dtype=F64, device=dev) for _ in range(2)],
+           "dv": [torch.zeros((lay.k_rows, D), dtype=F64, device=dev) for _ in range(2)]}
+    for b in range(sp.B):
+        cb, Mb = entry_case(c, b, M)
+        src = int(c["idx"][b])
+        s, n = lay.q_start[b], lay.q_len[b]
+        given = None if o16 is None else delta_out_ref(cb, o16[s:s + n], o_lo16[s:s + n], C_DELTA_CHAIN)
+        nq = 2 + sum(lay.q_len[i] for i in range(sp.B) if int(c["idx"][i]) == src) if sp.grouped else None
+        br = bwd_ref(cb, _stat_rows(lse32, sp, b, n).reshape(sp.H, n), Mb, delta_given=given, nq=nq)
+        ks, kn = lay.k_start[src], lay.k_len[src]
+        for i in range(2):
+            _stat_rows(out["delta"][i], sp, b, n).copy_(br["delta"][i].reshape(sp.H, n))
+            out["dq"][i][s:s + n] = br["dq"][i]
+            out["dk"][i][ks:ks + kn] += br["dk"][i]      # (one entry per source unless grouped)
+            out["dv"][i][ks:ks + kn] += br["dv"][i]
+    return {k: tuple(v) for k, v in out.items()}
+
+
+class RaggedBuffers(AttnBuffers):
+    """AttnBuffers for a RaggedSpec: the live rows of every entry at the layout's starts, NaN in the inputs' slack rows, the sentinel in
+    the outputs'; q_start / q_len / k_start / k_len as int32 device vectors (None for a dense side)."""
+
+    def __init__(self, c, device):
+        sp = c["sp"]
+        self.sp, self.dev = sp, device
+        lay = self.lay = ragged_layout(sp)
+        self.live = ragged_live(sp, device)
+        D = sp.H * 64
+        self.D, self.ld_stat = D, stat_ld(sp.Sq)
+        self.qkv = torch.full((max(lay.q_rows, lay.k_rows) + 7, 3 * D + 8), NAN, dtype=BF16, device=device)
+        self.q = self.qkv[4:4 + lay.q_rows, 8:8 + D]
+        self.k = self.qkv[4:4 + lay.k_rows, 8 + D:8 + 2 * D]
+        self.v = self.qkv[4:4 + lay.k_rows, 8 + 2 * D:8 + 3 * D]
+        self.do, self.do_parent = embed(torch.full((lay.q_rows, D), NAN, dtype=BF16, device=device), D + 8, 8, 4, 3, NAN)
+        for b, (s, n) in enumerate(zip(lay.q_start, lay.q_len)):
+            self.q[s:s + n] = c["q"][b, :n].reshape(n, D).to(device)
+            self.do[s:s + n] = c["do"][b, :n].reshape(n, D).to(device)
+        for u, (s, n) in enumerate(zip(lay.k_start, lay.k_len)):
+            self.k[s:s + n] = c["k"][u, :n].reshape(n, D).to(device)
+            self.v[s:s + n] = c["v"][u, :n].reshape(n, D).to(device)
+        self.keep = None if c["keep"] is None else c["keep"].to(device).contiguous()
+        self.bias = self.bias_parent = self.bias_t = self.bias_t_parent = None
+        self.kv_index = self.grp_start = self.grp_rows = None
+        if sp.grouped:
+            order = torch.sort(c["idx"].cpu(), stable=True).indices
+            start = torch.zeros(sp.U + 1, dtype=torch.int64)
+            start[1:] = torch.cumsum(torch.bincount(c["idx"].cpu(), minlength=sp.U), 0)
+            self.grp_start, self.grp_rows = start.to(I32).to(device), order.to(I32).to(device)
+        vec = lambda t: torch.tensor(t, dtype=I32, device=device)   # noqa: E731
+        self.q_start = self.q_len = self.k_start = self.k_len = None
+        if sp.q_len is not None:
+            self.q_start, self.q_len = vec(lay.q_start), vec(lay.q_len)
+        if sp.k_len is not None:
+            self.k_start, self.k_len = vec(lay.k_start), vec(lay.k_len)
+        self.begin()
+
+    def begin(self):
+        self.outs, self.given, self.sides, self.dead = {}, {}, {}, {}
+
+    def rows_out(self, name, side):
+        """a sentinel-filled bf16 output over the whole row buffer of the query ("q") or key ("k") side"""
+        self.sides[name] = side
+        return self.out16(name, self.lay.q_rows if side == "q" else self.lay.k_rows)
+
+    def stat(self, name, given=None, nan_padding=False):
+        """as AttnBuffers.stat; the kernels own columns [0, q_len[b]) only: the dead columns [q_len[b], Sq) hold what the padding holds
+        (given: the caller's values, NaN there by ragged_lse32)"""
+        v = AttnBuffers.stat(self, name, given, nan_padding)
+        if given is None:
+            if nan_padding:
+                v[:, :self.sp.Sq].masked_fill_(~self.live["stat"], NAN)
+            self.dead[name] = (v, nan_padding)
+        return v
+
+    def check_outside(self):
+        """AttnBuffers.check_outside, the statistics' dead columns and the slack rows of every row output kept their bits"""
+        AttnBuffers.check_outside(self)
+        for name, (v, is_nan) in self.dead.items():
+            dead = v[:, :self.sp.Sq][~self.live["stat"]]
+            ok = _nan_bits(dead) if is_nan else torch.equal(dead, torch.full_like(dead, SENTINEL))
+            assert ok, f"{name}: columns [q_len, Sq) were written"
+        for name, side in self.sides.items():
+            slack = self.outs[name][1][0][~self.live[side]]
+            assert torch.equal(slack, torch.full_like(slack, SENTINEL)), f"{name}: rows outside every sequence were written"
+
+
+RAGGED_VARIANTS = {"none": {}, "holes": {"mask": "holes"}, "holes+p0.1": {"mask": "holes", "p": 0.1}, "tail": {"mask": "tail"},
+                   "causal+holes+p0.1": {"mask": "holes", "p": 0.1, "causal": True}, "steep": {"mask": "holes", "score": "steep"}}
+# self-attention, both sides ragged: (route, B, Sq, Sk, q_len, k_len).  Each the padded shape of SHAPES that reaches the route, with
+# the lengths that reach the edge named
+RAGGED_SELF = [
+    ("packed", 3, 30, 30, (30, 3, 17), (30, 3, 17)),        # packed forward: a second tile of one row; an entry shorter than a tile
+    ("packed", 2, 64, 64, (64, 1), (64, 1)),                # the full chunk beside a single token
+    ("small", 1, 30, 30, (7,), (7,)),                       # B = 1: general kernels, 2 waves, the second wholly past q_len
+    ("resident", 2, 70, 130, (70, 33), (130, 64)),          # an entry with one chunk fewer than the padded shape; waves wholly past q_len
+    ("resident", 2, 70, 130, (1, 65), (1, 65)),             # one token; a second chunk of one key
+    ("streamed", 2, 40, 300, (40, 16), (300, 257)),         # last chunk of one key
+    ("causal", 3, 65, 65, (65, 64, 1), (65, 64, 1)),
+    ("causal", 2, 130, 130, (130, 17), (130, 17)),
+]
+RAGGED_RANGE = [("range", 3, 70, 130, (70, 5, 48)), ("range", 2, 40, 300, (40, 16))]      # queries ragged, keys dense, B = sources
+RAGGED_GROUPED = [
+    ("grouped", 5, 30, 130, 2, (1, 0, 1, 1, 0), (30, 1, 16, 17, 9)),
+    ("grouped_stream", 5, 40, 300, 2, (0, 1, 1, 0, 1), (40, 3, 33, 16, 1)),
+    ("grouped", 5, 30, 130, 3, (1, 0, 1, 1, 0), (30, 1, 16, 17, 9)),      # a third source that no row reads: its dk / dv are zeros
+]
+# o_lo on the non-ragged masked routes (the dense suite has o_lo on PLAIN problems only): dense rows, holes + p0.1
+O_LO_DENSE = [("resident", 2, 70, 130, 2, None, False), ("streamed", 2, 40, 300, 2, None, False),
+              ("grouped", 5, 30, 130, 2, (1, 0, 1, 1, 0), True), ("grouped_stream", 5, 40, 300, 2, (0, 1, 1, 0, 1), True)]
+
+
+def _lens_tag(q_len, k_len):
+    tag = "" if q_len is None else ":q" + ".".join(str(n) for n in q_len)
+    return tag + ("" if k_len is None or k_len == q_len else ":k" + ".".join(str(n) for n in k_len))
+
+
+def ragged_spec(route, B, Sq, Sk, U, idx, grouped, variant, q_len, k_len):
+    v = RAGGED_VARIANTS[variant]
+    name = variant + _lens_tag(q_len, k_len) + (f":U{U}" if grouped and U != 2 else "") + ("" if q_len is not None else ":dense")
+    return RaggedSpec(route, B, 2, Sq, Sk, U, idx, grouped, v.get("mask"), v.get("causal", False), v.get("p", 0.0), v.get("score", "randn"),
+                      False, name, q_len, k_len, "shuffled" if q_len is not None else "dense")
+
+
+def ragged_specs():
+    """Every case of the ragged suite (H = 2).  Self-attention: no mask, holes, holes + p0.1, steep per shape, causal + holes + p0.1 on the
+    squares; range mode: no mask, holes, holes + p0.1; grouped: holes, holes + p0.1, tail; the four dense o_lo cases: holes + p0.1."""
+    out = []
+    for route, B, Sq, Sk, ql, kl in RAGGED_SELF:
+        for variant in ("none", "holes", "holes+p0.1") + (("causal+holes+p0.1",) if Sq == Sk else ()) + ("steep",):
+            out.append(ragged_spec(route, B, Sq, Sk, B, None, False, variant, ql, kl))
+    for route, B, Sq, Sk, ql in RAGGED_RANGE:
+        for variant in ("none", "holes", "holes+p0.1"):
+            out.append(ragged_spec(route, B, Sq, Sk, B, None, False, variant, ql, None))
+    for route, B, Sq, Sk, U, idx, ql in RAGGED_GROUPED:
+        for variant in ("holes", "holes+p0.1", "tail"):
+            out.append(ragged_spec(route, B, Sq, Sk, U, idx, True, variant, ql, None))
+    for route, B, Sq, Sk, U, idx, grouped in O_LO_DENSE:
+        out.append(ragged_spec(route, B, Sq, Sk, U, idx, grouped, "holes+p0.1", None, None))
+    return out
+
+
+def norm_rel(got, ref):
+    """the measure of tests/test_hip_packing.py: ||got - ref|| / ||ref||"""
+    return float((got.double() - ref.double()).norm() / (ref.double().norm() + 1e-30))

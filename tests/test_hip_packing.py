@@ -3,7 +3,8 @@
 The padded path is itself pinned to the real reference by tests/golden (test_hip_modules.py); here the packed path must give the
 same values on every real token, forward and backward: the attention kernels with (start, length) arrays vs. padded rows + key
 mask, the embedding kernel through a row map, the text tower, the fusion tower with the device-computed slack block, and the
-whole pre-training step (also against the golden fixture of the reference itself)."""
+whole pre-training step (also against the golden fixture of the reference itself).
+Elementwise coverage of the attention kernels' ragged arguments: tests/test_hip_attention_packed_bounds.py (every element under an fp64 bound)."""
 import math
 
 import numpy as np

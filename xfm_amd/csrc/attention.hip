@@ -35,6 +35,8 @@ static int attn_check_grouped(const AttnArgs& a) {
   XFM_REQUIRE(a.Sq <= 64, "grouped attention needs Sq <= 64 (got %d)", a.Sq);   // (Sk > 256: the streamed-key kernels)
   XFM_REQUIRE(a.bias == nullptr && a.dbias == nullptr && a.causal == 0 && a.kv_index == nullptr,
               "grouped attention: no bias / causal mask / kv_index (the group index IS the key/value source)");
+  // (the grouped kernels address source g's keys as rows g * Sk .. + Sk: a k_start / k_len pair would be ignored, not honoured)
+  XFM_REQUIRE(a.k_start == nullptr && a.k_len == nullptr, "grouped attention: only the query side may be packed (k_start / k_len must be NULL)");
   return XFM_OK;
 }
 
