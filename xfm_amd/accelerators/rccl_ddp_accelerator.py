@@ -27,6 +27,7 @@ import torch
 import torch.distributed as dist
 
 from .. import functional as Fx
+from ..side_stream import _WgradStream
 from .accelerator import Accelerator
 
 
@@ -197,15 +198,8 @@ class RCCLDDPAccelerator(Accelerator):
         every stream of the step is created and used once, in an order chosen for the sharing it produces; `nccl` stands for the
         set-up broadcast (ProcessGroupNCCL's first collective = its stream's first use)."""
         from ..model_pretrain import _side_stream
-        from ..xroberta import _WgradStream
         dev = torch.device("cuda", local_rank)
         main = torch.cuda.current_stream(dev)
-
-        def wside(of):
-            key = (dev.index, of.cuda_stream)
-            if key not in _WgradStream._streams:
-                _WgradStream._streams[key] = torch.cuda.Stream(device=dev, priority=_WgradStream.priority)
-            return _WgradStream._streams[key]
 
         for name in [t.strip() for t in order.split(",") if t.strip()]:
             if name == "nccl":
@@ -215,9 +209,9 @@ class RCCLDDPAccelerator(Accelerator):
             if name == "text":
                 st = _side_stream(dev)
             elif name == "wmain":
-                st = wside(main)
+                st = _WgradStream.side_of(dev, main)
             elif name == "wtext":
-                st = wside(_side_stream(dev))
+                st = _WgradStream.side_of(dev, _side_stream(dev))
             elif name == "cast":
                 if self.arena._cast_stream is None:
                     self.arena._cast_stream = torch.cuda.Stream(device=dev)
@@ -350,15 +344,13 @@ class RCCLDDPAccelerator(Accelerator):
         self._comm_stream.wait_stream(cur)
         if extra_stream is not None:  # weight-gradient GEMMs of the range still in flight on their own stream
             self._comm_stream.wait_stream(extra_stream)
-        # Parameter gradients are also written on the weight-gradient side streams (xroberta._WgradStream: one per launch stream) by
+        # Parameter gradients are also written on the weight-gradient side streams (side_stream._WgradStream: one per launch stream) by
         # launch sites that re-join only at the END of the backward pass (join_at_end: the LM head's two weight gradients, whose
         # parameters lie inside the fusion tower's range; ops._LinearSlotFn).  A range leaves only with its gradients final, so the
         # exchange waits for everything those streams hold at this point, whichever stream the writer used -- not just the one whose
         # FIFO happens to be shared with the tower (advisor finding, round 4).
-        from ..xroberta import _WgradStream
-        dev = self.arena.grad.device.index
-        for (d, _), side in list(_WgradStream._streams.items()):
-            if d == dev and side is not extra_stream:
+        for side in _WgradStream.sides(self.arena.grad.device.index).values():
+            if side is not extra_stream:
                 self._comm_stream.wait_stream(side)
         with torch.cuda.stream(self._comm_stream):
             n_before = len(self._pending)
@@ -387,9 +379,8 @@ class RCCLDDPAccelerator(Accelerator):
         """N = 1: a tower's backward is over (its weight gradients have been joined into the current stream): its ranges' share of the
         gradient norm runs on the tower's weight-gradient side stream (behind whatever that stream still holds for the tower, e.g. the LM
         head's weight gradients that re-join at the end of backward) while the launch stream goes on with the next tower's backward."""
-        from ..xroberta import _WgradStream
         cur = torch.cuda.current_stream()
-        side = _WgradStream._streams.get((self.arena.grad.device.index, cur.cuda_stream))
+        side = _WgradStream.sides(self.arena.grad.device.index).get(cur.cuda_stream)
         if side is None:
             return self._sumsq_ranges(_clip(self._ranges, *rng))
         side.wait_stream(cur)

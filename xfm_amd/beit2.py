@@ -16,6 +16,7 @@ import torch.nn as nn
 from . import functional as Fx
 from .arena import LinearSlot, OwnsArena, ParamArena
 from .ops import linear_slot
+from .side_stream import _WgradStream
 
 
 class BlockMaskGenerator:
@@ -191,7 +192,6 @@ class _TrunkFn(torch.autograd.Function):
         # weights alone: all 24 launches go to the second stream up front and run under the first block's GEMMs
         ahead = None
         if rel_pos and x.is_cuda and _RELPOS_AHEAD:
-            from .xroberta import _WgradStream
             pre = _WgradStream(x.device)
             if pre.on:
                 ahead = []
@@ -257,7 +257,6 @@ class _TrunkFn(torch.autograd.Function):
         if ctx.pooled:
             dy = Fx.pool_rows_bwd(dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16), B, N)
         dstream = torch.zeros((M, D), dtype=torch.float32, device=dy.device)
-        from .xroberta import _WgradStream
         wg = _WgradStream(dy.device, "vit bwd")
         done = len(blocks)
         ddense_all = None

@@ -6,7 +6,7 @@ What the reference does with `use_cache` / `past_key_values` (models/xroberta.py
     write inside the attention kernel.  It also holds the K | V projections of the encoder states of every cross-attention layer, which
     the reference recomputes at every step (xroberta.py:224-226), keyed by the identity of those states.
   * `cached_forward`: RobertaModel / BertModel.forward with a cache.  Without a past the prompt runs through the causal kernels of the
-    ordinary forward (the same calls as `_EncoderFn.forward`, in inference form) and its K / V rows are kept; with a past, ONE new token per
+    ordinary forward (the shared layer body, `roberta_layer.forward_tail`, in inference form) and its K / V rows are kept; with a past, ONE new token per
     row runs through `Fx.decode_attn` in place of the two `Fx.attn_fwd` calls.
   * `GenerationMixin`: `prepare_inputs_for_generation`, `_reorder_cache`, `_generate_no_beam_search` with the reference's signatures;
     one `Fx.next_token` launch per step does the penalty, the choice, the score and the finished-row bookkeeping on the device.
@@ -17,6 +17,7 @@ from types import SimpleNamespace
 import torch
 
 from . import functional as Fx
+from .roberta_layer import NO_DROPS, forward_tail
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -96,9 +97,9 @@ def _embed_step(model, input_ids, past_len, f32):
 
 
 def _run_layers(model, x, xres, cache, B, T, key_keep, enc_keep, enc_index, f32):
-    """The layer loop of _EncoderFn.forward in inference form (no dropout, nothing saved), kernel for kernel: gemm_nt, ln_post_fwd and the
-    GELU-epilogue GEMM; T == 1: both attentions are Fx.decode_attn on the cache; T > 1 (the prompt, empty cache): Fx.attn_fwd, causal, and
-    the K | V columns of the QKV projection are copied into the cache rows."""
+    """The layer loop in inference form: roberta_layer.forward_tail with no dropout and nothing saved behind this path's own attentions.
+    T == 1: both are Fx.decode_attn on the cache; T > 1 (the prompt, empty cache): Fx.attn_fwd, causal, and the K | V columns of the QKV
+    projection are copied into the cache rows."""
     cfg = model.config
     D, H = cfg.hidden_size, cfg.num_attention_heads
     scale = 1.0 / math.sqrt(D // H)
@@ -114,28 +115,13 @@ def _run_layers(model, x, xres, cache, B, T, key_keep, enc_keep, enc_index, f32)
         else:
             c1, _ = Fx.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, H, T, T, scale, key_keep=key_keep, causal=True)
             buf[:, :T] = qkv[:, D:].view(B, T, 2 * D)
-        h1 = Fx.gemm_nt(c1, s["o"].wb, s["o"].b)
-        ln1 = layer.attention.output.LayerNorm
-        y1, _, _, _, *tw = Fx.ln_post_fwd(h1, xres, ln1.weight, ln1.bias, ln1.eps, f32=f32)
-        yres = tw[0] if f32 else y1
-        y2 = y1
+        cross = None
         if layer.has_cross_attention and li in cache.cross_kv:
-            kv = cache.cross_kv[li]
-            q2 = Fx.gemm_nt(y1, s["q2"].wb, s["q2"].b)
-            if T == 1:
-                c2 = Fx.decode_attn(q2, kv[:, :D], kv[:, D:], Nenc, H, scale, Sk=Nenc, key_keep=enc_keep, kv_index=enc_index)
-            else:
-                c2, _ = Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], B, H, T, Nenc, scale, key_keep=enc_keep, kv_index=enc_index)
-            h2 = Fx.gemm_nt(c2, s["o2"].wb, s["o2"].b)
-            ln2 = layer.crossattention.output.LayerNorm
-            y2, _, _, _, *tw = Fx.ln_post_fwd(h2, yres, ln2.weight, ln2.bias, ln2.eps, f32=f32)
-            yres = tw[0] if f32 else y2
-        hact, _ = Fx.gemm_nt(y2, s["i"].wb, s["i"].b, epi=Fx.EPI_GELU)
-        h3 = Fx.gemm_nt(hact, s["out"].wb, s["out"].b)
-        ln3 = layer.output.LayerNorm
-        y3, _, _, _, *tw = Fx.ln_post_fwd(h3, yres, ln3.weight, ln3.bias, ln3.eps, f32=f32)
-        x = y3
-        xres = tw[0] if f32 else y3
+            def cross(q2, kv=cache.cross_kv[li]):
+                if T == 1:
+                    return kv, Fx.decode_attn(q2, kv[:, :D], kv[:, D:], Nenc, H, scale, Sk=Nenc, key_keep=enc_keep, kv_index=enc_index), None, None
+                return kv, Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], B, H, T, Nenc, scale, key_keep=enc_keep, kv_index=enc_index)[0], None, None
+        x, xres, _ = forward_tail(layer, c1, xres, NO_DROPS, f32, cross, save=False)
     return x, (xres if f32 else None)
 
 

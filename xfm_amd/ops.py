@@ -5,13 +5,10 @@ import math
 import torch
 
 from . import functional as Fx
+from .arena import grad_of as grad_view   # gradient view of a parameter inside the arena (marks it live)
+from .side_stream import _WgradStream
 
 BF16, F32 = torch.bfloat16, torch.float32
-
-
-def grad_view(p):
-    from .arena import grad_of
-    return grad_of(p)
 
 
 class _LinearSlotFn(torch.autograd.Function):
@@ -36,7 +33,6 @@ class _LinearSlotFn(torch.autograd.Function):
             dyp[:, :s.N] = dy2
             dy2 = dyp
         if dy2.is_cuda:   # the weight gradient leaves the chain: second stream, re-joined when the backward pass is over
-            from .xroberta import _WgradStream
             wg = _WgradStream(dy2.device)
             wg.gemm_tn(dy2, ctx.x2, s.dw, n=s.N, dbias=s.db)
             wg.join_at_end()
@@ -261,7 +257,6 @@ class _LMHeadCEFn(torch.autograd.Function):
             dlogits = Fx.ce_bwd(logits, V, labels, lse, scale, logits.shape[1])
         # the two weight gradients (the 50265 x 768 one takes 310 us) go to the second stream and re-join at the end of the backward
         # pass: they run under the fusion tower's latency-bound activation-gradient chain instead of in front of it
-        from .xroberta import _WgradStream
         wg = _WgradStream(x.device)
         wg.gemm_tn(dlogits, y, sv.dw, n=V, dbias=sv.db)
         # dgrad of the vocabulary projection: K = 50304 against a 960 x 768 output -- K is sliced over the grid instead of 90 workgroups

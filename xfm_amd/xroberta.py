@@ -20,6 +20,8 @@ from .arena import LinearSlot, OwnsArena, ParamArena
 from .beit2 import _Affine, arena_note_grad, arena_note_use
 from .decode import GenerationMixin
 from .ops import grad_view, lm_head_ce, lm_head_logits
+from .roberta_layer import backward_tail, cross_bwd_split, forward_tail
+from .side_stream import _WgradStream
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -47,6 +49,14 @@ _seed_counter = [0]
 def _next_seed():
     _seed_counter[0] += 1
     return ((torch.initial_seed() & 0xFFFFFFFF) << 32) | (_seed_counter[0] & 0xFFFFFFFF)
+
+
+def _layer_drops(p_att, p_hid, cross):
+    """A layer's drop tuples (d_att, d_h1, d_att2, d_h2, d_h3), seeds drawn in that order (the two cross entries: None and no seed
+    without cross-attention; the counter advances in eval mode too)."""
+    d_att, d_h1 = Fx.drop_params(p_att, _next_seed()), Fx.drop_params(p_hid, _next_seed())
+    d_att2, d_h2 = (Fx.drop_params(p_att, _next_seed()), Fx.drop_params(p_hid, _next_seed())) if cross else (None, None)
+    return d_att, d_h1, d_att2, d_h2, Fx.drop_params(p_hid, _next_seed())
 
 
 class _Lin(nn.Module):
@@ -223,180 +233,6 @@ class RobertaEncoder(nn.Module):
         self.layer = nn.ModuleList([RobertaLayer(config, i) for i in range(config.num_hidden_layers)])
 
 
-from . import marks as _marks  # noqa: E402
-
-
-class _DeferredCall:
-    """One-shot work of a _WgradStream flush."""
-    persistent = False
-
-    def __init__(self, fn, keep=()):
-        self.fn, self.keep = fn, tuple(keep)
-
-    def run(self):
-        self.fn()
-
-
-class _WgradStream:
-    """Weight-gradient GEMMs of a tower's backward on a second HIP stream.  dW only feeds the optimizer / all-reduce, so the
-    dY^T X products need not sit on the activation-gradient critical path: at the fusion / text towers' sizes (M = 7680 / 1920 rows)
-    neither the dgrad nor the wgrad kernels fill the 256 CUs on their own, and the two chains overlap.  Every launch waits for an
-    event recorded on the main stream after its dY was produced; the tensors it reads are kept alive until the main stream has
-    re-joined (the caching allocator reuses freed blocks in main-stream order only)."""
-    _streams = {}
-    enabled = os.environ.get("XFM_WGRAD_STREAM", "1") != "0"
-    priority = int(os.environ.get("XFM_WGRAD_PRIO", "0"))  # HIP stream priority of the second stream (lower number = served first)
-
-    def __init__(self, device, label=None):
-        self.label = label
-        if label is not None:
-            _marks.mark(label + " begin")
-        self.main = torch.cuda.current_stream(device)
-        if label is not None:   # a tower's backward starts: its gradient writes must follow a pending asynchronous zero_grad (arena.grads_ready)
-            from .arena import grads_ready
-            grads_ready(device)
-        self.on = _WgradStream.enabled
-        if self.on:
-            # one side stream per LAUNCH stream: the text tower's backward runs on its own stream next to the ViT's, and its small
-            # weight gradients must not queue (FIFO) behind the ViT's grouped launch on a shared side stream
-            key = (device.index if device.index is not None else torch.cuda.current_device(), self.main.cuda_stream)
-            if key not in _WgradStream._streams:
-                _WgradStream._streams[key] = torch.cuda.Stream(device=device, priority=_WgradStream.priority)
-            self.side = _WgradStream._streams[key]
-            self.side.wait_stream(self.main)  # arena state (zeroed grads, earlier kernels) is visible to the side stream
-        self.keep = []
-        self.queue = []
-        self.reduces = []
-
-    def defer_tn(self, dy, x, dw, dbias=None):
-        """Queue dw += dy^T @ x (dbias += column sums of dy) for the next flush(): everything queued -- all over the same M rows --
-        runs as ONE grouped launch (Fx.gemm_tn_group: whole 256 x 256 tiles with one owner each instead of 7 M-split planes and a
-        reduce per projection; the 48 weight gradients of the ViT trunk: 5.2 -> 3.9 ms).  The queue holds dy / x alive."""
-        self.queue.append((dy, x, dw, dbias))
-
-    def defer_call(self, fn, keep=()):
-        """fn() runs with the next flush() (second stream, after everything the launch stream holds then): parameter-gradient kernels
-        that nothing on the activation-gradient chain waits for (the relative-position table gradients of the ViT blocks, the batched
-        LayerNorm folds of the layer executor).  `keep`: the tensors it touches."""
-        self.reduces.append(_DeferredCall(fn, keep))
-
-    def defer_reduces(self, rq):
-        """A Fx.ReduceQueue: whatever LayerNorm backward kernels have queued on it is folded by every flush() until the join."""
-        self.reduces.append(rq)
-
-    def _run_reduces(self, reduces):
-        for work in reduces:
-            work.run()
-
-    def flush(self):
-        reduces = self.reduces
-        self.reduces = [r for r in reduces if getattr(r, "persistent", False)]   # a ReduceQueue stays registered (more kernels will append to it)
-        if reduces and not self.queue:
-            if not self.on:
-                return self._run_reduces(reduces)
-            ev = torch.cuda.Event()
-            ev.record(self.main)
-            self.side.wait_event(ev)
-            self.keep.append(reduces)
-            with torch.cuda.stream(self.side):
-                self._run_reduces(reduces)
-            return
-        if not self.queue:
-            return
-        items, self.queue = self.queue, []
-        by_m = {}
-        for it in items:   # one grouped launch per distinct row count (a tower's projections share M; the K/V projections of the image states
-            by_m.setdefault(it[0].shape[0], []).append(it)   # and the pruned last layer have their own)
-        if not self.on:
-            self._run_reduces(reduces)
-            for group in by_m.values():
-                Fx.gemm_tn_group(group)
-            return
-        ev = torch.cuda.Event()
-        ev.record(self.main)
-        self.side.wait_event(ev)
-        self.keep.append((items, reduces))
-        with torch.cuda.stream(self.side):
-            self._run_reduces(reduces)
-            for group in by_m.values():
-                Fx.gemm_tn_group(group)
-
-    def gemm_tn(self, dy, x, dw, **kw):
-        if not self.on:
-            return Fx.gemm_tn(dy, x, dw, **kw)
-        ev = torch.cuda.Event()
-        ev.record(self.main)
-        self.side.wait_event(ev)
-        self.keep.append((dy, x))
-        with torch.cuda.stream(self.side):
-            Fx.gemm_tn(dy, x, dw, **kw)
-
-    def project(self, x, slot):
-        """x @ slot.W^T + b on the side stream; returns (tensor, event) for take()."""
-        if not self.on:
-            return Fx.gemm_nt(x, slot.wb, slot.b), None
-        with torch.cuda.stream(self.side):
-            y = Fx.gemm_nt(x, slot.wb, slot.b)
-            ev = torch.cuda.Event()
-            ev.record(self.side)
-        y.record_stream(self.main)  # allocated on the side stream, consumed on the main one
-        return y, ev
-
-    def take(self, pair):
-        y, ev = pair
-        if ev is not None:
-            self.main.wait_event(ev)
-        return y
-
-    def run(self, fn, keep=()):
-        """fn() on the side stream, after everything enqueued on the main stream so far; `keep` = the tensors it touches."""
-        if not self.on:
-            return fn()
-        ev = torch.cuda.Event()
-        ev.record(self.main)
-        self.side.wait_event(ev)
-        self.keep.append(tuple(keep))
-        with torch.cuda.stream(self.side):
-            return fn()
-
-    def sync_side(self):
-        """The launch stream waits for what the second stream has been given so far (queued weight gradients are not launched)."""
-        if self.on:
-            self.main.wait_stream(self.side)
-
-    def join_at_end(self):
-        """Like join(), but the launch stream re-joins when the whole backward pass is over (an engine callback, as
-        model_pretrain._JoinAfterBackward): the weight gradients given to the second stream here need not finish before the NEXT node's
-        activation gradients start -- only before anyone reads the parameter gradients.  Only inside a backward pass."""
-        self.flush()
-        if self.on:
-            main, side, keep = self.main, self.side, self.keep
-
-            def rejoin():
-                main.wait_stream(side)
-                # the callback runs on the thread (and current stream) that called backward(): if this node ran on another stream (the
-                # text tower's, replayed by autograd), that caller -- the optimizer, the gradient norm, the final all-reduce -- must wait
-                # for these weight gradients too, whatever order the end-of-backward callbacks run in
-                cur = torch.cuda.current_stream(main.device)
-                if cur != main:
-                    cur.wait_stream(side)
-                keep.clear()
-            torch.autograd.Variable._execution_engine.queue_callback(rejoin)
-            self.keep = []
-        else:
-            self.keep.clear()
-
-    def join(self):
-        if self.label is not None:
-            _marks.mark(self.label + " chain end")
-        self.flush()
-        if self.on:
-            self.main.wait_stream(self.side)
-        self.keep.clear()
-        if self.label is not None:
-            _marks.mark(self.label + " end")
-
-
 def _grad_pair(dy, dy32, f32):
     """The two gradient edges of a tower output (bf16 tensor, fp32 twin) as the (dy_a bf16, dy_b) pair the layer loop starts from:
     dy_b is the fp32 part with the fp32 stream on (None when nobody read the twin), None otherwise."""
@@ -470,49 +306,28 @@ class _EncoderFn(torch.autograd.Function):
                     kv_ready[li] = pre.project(enc, layer._s["kv2"])
         for li in range(lo, hi):
             layer = model.encoder.layer[li]
-            s = layer._s
-            att, co = layer.attention, None
-            d_att, d_h1 = Fx.drop_params(p_att, _next_seed()), Fx.drop_params(p_hid, _next_seed())
+            s, cross = layer._s, None
+            drops = _layer_drops(p_att, p_hid, layer.has_cross_attention and enc is not None)
             qkv = Fx.gemm_nt(x, s["qkv"].wb, s["qkv"].b)
             c1, lse1 = Fx.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, H, T, T, scale, key_keep=key_keep,
-                                          causal=causal, drop=d_att, q_pack=qp, k_pack=qp, zero_fill=zf)
-            h1 = Fx.gemm_nt(c1, s["o"].wb, s["o"].b)
-            ln1 = att.output.LayerNorm
-            y1, z1, m1, r1, *tw = Fx.ln_post_fwd(h1, xres, ln1.weight, ln1.bias, ln1.eps, d_h1, f32=f32)
-            yres = tw[0] if f32 else y1
-            rec = {"x": x, "qkv": qkv, "c1": c1, "lse1": lse1, "z1": z1, "m1": m1, "r1": r1, "y1": y1, "d_att": d_att, "d_h1": d_h1}
-            y2 = y1
-            if layer.has_cross_attention and enc is not None:
-                co = layer.crossattention
-                d_att2, d_h2 = Fx.drop_params(p_att, _next_seed()), Fx.drop_params(p_hid, _next_seed())
-                q2 = Fx.gemm_nt(y1, s["q2"].wb, s["q2"].b)
-                kv = pre.take(kv_ready.pop(li))
-                if xq is not None:  # RANGE mode: sequences laid out image by image -> one ragged problem per image, full query tiles
-                    c2, lse2, c2lo = Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], enc.shape[0] // Nenc, H, xq[2], Nenc, scale, key_keep=enc_keep,
-                                                 drop=d_att2, q_pack=(xq[0], xq[1]), zero_fill=zf, lo=True)
-                elif groups is not None:  # one workgroup per (image, head): K/V staged once for every row that reads it
-                    # (lo: the low half of the output -- the backward's delta = dO . (O + Olo) then needs no sweep over the keys)
-                    c2, lse2, c2lo = Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], B, H, T, Nenc, scale, key_keep=enc_keep, drop=d_att2, groups=groups,
-                                                 q_pack=qp, zero_fill=zf, lo=True)
-                elif pack is not None:
-                    raise NotImplementedError("packed rows with cross-attention need the grouped kernels (T <= 64) and an encoder_batch_index")
-                else:
-                    c2, lse2 = Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], B, H, T, Nenc, scale, key_keep=enc_keep, drop=d_att2, kv_index=enc_index)
-                    c2lo = None
-                h2 = Fx.gemm_nt(c2, s["o2"].wb, s["o2"].b)
-                ln2 = co.output.LayerNorm
-                y2, z2, m2, r2, *tw = Fx.ln_post_fwd(h2, yres, ln2.weight, ln2.bias, ln2.eps, d_h2, f32=f32)
-                yres = tw[0] if f32 else y2
-                rec.update(q2=q2, kv=kv, c2=c2, c2lo=c2lo, lse2=lse2, z2=z2, m2=m2, r2=r2, y2=y2, d_att2=d_att2, d_h2=d_h2)
-            d_h3 = Fx.drop_params(p_hid, _next_seed())
-            hact, u = Fx.gemm_nt(y2, s["i"].wb, s["i"].b, epi=Fx.EPI_GELU)
-            h3 = Fx.gemm_nt(hact, s["out"].wb, s["out"].b)
-            ln3 = layer.output.LayerNorm
-            y3, z3, m3, r3, *tw = Fx.ln_post_fwd(h3, yres, ln3.weight, ln3.bias, ln3.eps, d_h3, f32=f32)
-            rec.update(hact=hact, u=u, z3=z3, m3=m3, r3=r3, d_h3=d_h3, cross=co is not None)
+                                          causal=causal, drop=drops[0], q_pack=qp, k_pack=qp, zero_fill=zf)
+            if drops[2] is not None:
+                def cross(q2, li=li, d_att2=drops[2]):
+                    kv = pre.take(kv_ready.pop(li))
+                    if xq is not None:  # RANGE mode: sequences laid out image by image -> one ragged problem per image, full query tiles
+                        return (kv,) + Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], enc.shape[0] // Nenc, H, xq[2], Nenc, scale, key_keep=enc_keep,
+                                                   drop=d_att2, q_pack=(xq[0], xq[1]), zero_fill=zf, lo=True)
+                    if groups is not None:  # one workgroup per (image, head): K/V staged once for every row that reads it
+                        # (lo: the low half of the output -- the backward's delta = dO . (O + Olo) then needs no sweep over the keys)
+                        return (kv,) + Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], B, H, T, Nenc, scale, key_keep=enc_keep, drop=d_att2, groups=groups,
+                                                   q_pack=qp, zero_fill=zf, lo=True)
+                    if pack is not None:
+                        raise NotImplementedError("packed rows with cross-attention need the grouped kernels (T <= 64) and an encoder_batch_index")
+                    return (kv,) + Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], B, H, T, Nenc, scale, key_keep=enc_keep, drop=d_att2, kv_index=enc_index) + (None,)
+            y3, yres, rec = forward_tail(layer, c1, xres, drops, f32, cross)
+            rec.update(x=x, qkv=qkv, lse1=lse1, li=li)
             saved.append(rec)
-            x = y3
-            xres = tw[0] if f32 else y3
+            x, xres = y3, yres
         ctx.saved, ctx.model, ctx.enc = saved, model, enc
         if grad_batch is not None and (enc is not None or not 0 < grad_batch <= B):
             raise ValueError("grad_batch is for self-attention-only passes: 0 < grad_batch <= batch")
@@ -529,12 +344,10 @@ class _EncoderFn(torch.autograd.Function):
         lo, hi, causal, B, T, Nenc, key_keep, enc_keep, need_dx, need_denc, scale, enc_index, groups, grad_batch = ctx.meta
         cfg = model.config
         D, H = cfg.hidden_size, cfg.num_attention_heads
-        g = grad_view
         f32 = _F32_STREAM
         dy_a, dy_b = _grad_pair(dy, dy32, f32)
         dy = dy_a
         wg = _WgradStream(dy.device, "fusion bwd" if enc is not None else "text bwd")
-        B_full = B
         pack = ctx.pack
         rows_full = dy_a.shape[0]
         if grad_batch is not None and grad_batch < B:
@@ -565,61 +378,43 @@ class _EncoderFn(torch.autograd.Function):
         dkv_all = torch.empty((enc.shape[0], len(cross_layers) * 2 * D), dtype=BF16, device=dy.device) if concat_k else None
         if need_denc and not concat_k:
             denc32 = torch.zeros((enc.shape[0], D), dtype=F32, device=dy.device)
+
+        def cross_bwd(dc2, r):
+            kv = r["kv"]
+            dq2 = new_grad(r["q2"])
+            if per_image:  # dK/dV accumulated over each image's rows in registers, written once per image
+                if concat_k:
+                    j = cross_layers.index(r["li"])
+                    dkv = dkv_all[:, j * 2 * D:(j + 1) * 2 * D]
+                else:
+                    dkv = torch.empty((enc.shape[0], 2 * D), dtype=BF16, device=dq2.device)
+                if xq is not None:
+                    args = (dc2, r["q2"], kv[:, :D], kv[:, D:], r["c2"], r["lse2"], dq2, dkv[:, :D], dkv[:, D:], enc.shape[0] // Nenc, H,
+                            xq[2], Nenc, scale)
+                    kw = dict(key_keep=enc_keep, drop=r["d_att2"], q_pack=(xq[0], xq[1]), o_lo=r["c2lo"])
+                else:
+                    args = (dc2, r["q2"], kv[:, :D], kv[:, D:], r["c2"], r["lse2"], dq2, dkv[:, :D], dkv[:, D:], B, H, T, Nenc, scale)
+                    kw = dict(key_keep=enc_keep, drop=r["d_att2"], groups=groups, q_pack=qp, o_lo=r["c2lo"])
+                cross_bwd_split(wg, args, kw)
+            else:
+                dkv = torch.empty((B * Nenc, 2 * D), dtype=BF16, device=dq2.device)  # per query row
+                Fx.attn_bwd(dc2, r["q2"], kv[:, :D], kv[:, D:], r["c2"], r["lse2"], dq2, dkv[:, :D], dkv[:, D:], B, H, T, Nenc,
+                            scale, key_keep=enc_keep, drop=r["d_att2"], kv_index=enc_index)
+                if enc_index is not None:  # fold onto the unique key/value sources
+                    dkv = Fx.rows_index_sum(dkv, enc_index, enc.shape[0] // Nenc, Nenc)
+            return dq2, dkv
+
+        def add_denc(dkv, r):
+            s = model.encoder.layer[r["li"]]._s
+            if per_image:  # dkv is produced on the second stream: its consumer follows it there
+                wg.run(lambda dkv=dkv, s=s: Fx.gemm_nt(dkv, s["kv2"].wt, epi=Fx.EPI_F32_ACC, out=denc32, n=s["kv2"].K), keep=(dkv,))
+            else:
+                Fx.gemm_nt(dkv, s["kv2"].wt, epi=Fx.EPI_F32_ACC, out=denc32, n=s["kv2"].K)
+
         for li in reversed(range(lo, hi)):
             layer = model.encoder.layer[li]
             s, r = layer._s, ctx.saved[li - lo]
-            ln3 = layer.output.LayerNorm
-            dh3, dres3 = Fx.ln_post_bwd(dy_a, r["z3"], r["m3"], r["r3"], ln3.weight, g(ln3.weight), g(ln3.bias), s["out"].db,
-                                        dy2=dy_b, drop=r["d_h3"])
-            wg.gemm_tn(dh3, r["hact"], s["out"].dw)
-            du = Fx.gemm_nt(dh3, s["out"].wt, epi=Fx.EPI_DGELU, aux=r["u"], n=s["out"].K)
-            y2 = r["y2"] if r["cross"] else r["y1"]
-            wg.gemm_tn(du, y2, s["i"].dw, dbias=s["i"].db)
-            d1a, d1b = Fx.gemm_nt(du, s["i"].wt, n=s["i"].K), dres3
-            if r["cross"]:
-                ln2 = layer.crossattention.output.LayerNorm
-                dh2, dres2 = Fx.ln_post_bwd(d1a, r["z2"], r["m2"], r["r2"], ln2.weight, g(ln2.weight), g(ln2.bias), s["o2"].db,
-                                            dy2=d1b, drop=r["d_h2"])
-                wg.gemm_tn(dh2, r["c2"], s["o2"].dw)
-                dc2 = Fx.gemm_nt(dh2, s["o2"].wt, n=s["o2"].K)
-                kv = r["kv"]
-                dq2 = new_grad(r["q2"])
-                if per_image:  # dK/dV accumulated over each image's rows in registers, written once per image
-                    if concat_k:
-                        j = cross_layers.index(li)
-                        dkv = dkv_all[:, j * 2 * D:(j + 1) * 2 * D]
-                    else:
-                        dkv = torch.empty((enc.shape[0], 2 * D), dtype=BF16, device=dq2.device)
-                    # dQ stays on the activation-gradient chain; dK/dV (they only feed the K/V weight gradient and, after the last
-                    # layer, the gradient of the image states) run next to the weight-gradient GEMMs on the second stream
-                    if xq is not None:
-                        args = (dc2, r["q2"], kv[:, :D], kv[:, D:], r["c2"], r["lse2"], dq2, dkv[:, :D], dkv[:, D:], enc.shape[0] // Nenc, H,
-                                xq[2], Nenc, scale)
-                        kw = dict(key_keep=enc_keep, drop=r["d_att2"], q_pack=(xq[0], xq[1]), o_lo=r["c2lo"])
-                    else:
-                        args = (dc2, r["q2"], kv[:, :D], kv[:, D:], r["c2"], r["lse2"], dq2, dkv[:, :D], dkv[:, D:], B, H, T, Nenc, scale)
-                        kw = dict(key_keep=enc_keep, drop=r["d_att2"], groups=groups, q_pack=qp, o_lo=r["c2lo"])
-                    delta = Fx.attn_bwd(*args, phase=1, **kw)
-                    wg.run(lambda: Fx.attn_bwd(*args, phase=2, delta=delta, **kw), keep=args[:9] + (delta,))
-                else:
-                    dkv = torch.empty((B * Nenc, 2 * D), dtype=BF16, device=dq2.device)  # per query row
-                    Fx.attn_bwd(dc2, r["q2"], kv[:, :D], kv[:, D:], r["c2"], r["lse2"], dq2, dkv[:, :D], dkv[:, D:], B, H, T, Nenc,
-                                scale, key_keep=enc_keep, drop=r["d_att2"], kv_index=enc_index)
-                    if enc_index is not None:  # fold onto the unique key/value sources
-                        dkv = Fx.rows_index_sum(dkv, enc_index, enc.shape[0] // Nenc, Nenc)
-                wg.gemm_tn(dq2, r["y1"], s["q2"].dw, dbias=s["q2"].db)
-                wg.gemm_tn(dkv, enc, s["kv2"].dw, dbias=s["kv2"].db)
-                if need_denc and not concat_k:
-                    if per_image:  # dkv is produced on the second stream: its consumer follows it there
-                        wg.run(lambda dkv=dkv, s=s: Fx.gemm_nt(dkv, s["kv2"].wt, epi=Fx.EPI_F32_ACC, out=denc32, n=s["kv2"].K), keep=(dkv,))
-                    else:
-                        Fx.gemm_nt(dkv, s["kv2"].wt, epi=Fx.EPI_F32_ACC, out=denc32, n=s["kv2"].K)
-                d1a, d1b = Fx.gemm_nt(dq2, s["q2"].wt, n=s["q2"].K), dres2
-            ln1 = layer.attention.output.LayerNorm
-            dh1, dres1 = Fx.ln_post_bwd(d1a, r["z1"], r["m1"], r["r1"], ln1.weight, g(ln1.weight), g(ln1.bias), s["o"].db,
-                                        dy2=d1b, drop=r["d_h1"])
-            wg.gemm_tn(dh1, r["c1"], s["o"].dw)
-            dc1 = Fx.gemm_nt(dh1, s["o"].wt, n=s["o"].K)
+            dc1, dres1 = backward_tail(layer, r, dy_a, dy_b, wg, enc, cross_bwd, add_denc if need_denc and not concat_k else None)
             qkv = r["qkv"]
             dqkv = new_grad(qkv)
             Fx.attn_bwd(dc1, qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], r["c1"], r["lse1"], dqkv[:, :D], dqkv[:, D:2 * D],
@@ -673,43 +468,27 @@ class _LastLayerRowsFn(torch.autograd.Function):
         pre = _WgradStream(x.device)
         kv_pair = pre.project(enc, s["kv2"]) if cross else None
         groups = Fx.kv_groups(enc_index, enc.shape[0] // Nenc) if cross else None
-        d_att, d_h1 = Fx.drop_params(p_att, _next_seed()), Fx.drop_params(p_hid, _next_seed())
+        drops = _layer_drops(p_att, p_hid, cross)
         wqkv, bqkv = s["qkv"].wb, s["qkv"].b
         kvs = Fx.gemm_nt(x, wqkv[D:3 * D], bqkv[D:3 * D])                      # K | V of every row
         xs = Fx.rows_gather(x, rows)
         xres = Fx.rows_gather(x32.contiguous(), rows) if ctx.twin_in else xs   # the selected rows' residual, un-rounded when the twin exists
         qs = Fx.gemm_nt(xs, wqkv[:D], bqkv[:D])                                # Q of the selected rows
-        c1, lse1 = Fx.attn_fwd(qs, kvs[:, :D], kvs[:, D:], B, H, Tq, T, scale, drop=d_att, q_pack=sel, k_pack=kp, zero_fill=False)
-        h1 = Fx.gemm_nt(c1, s["o"].wb, s["o"].b)
-        ln1 = layer.attention.output.LayerNorm
-        y1, z1, m1, r1, *tw = Fx.ln_post_fwd(h1, xres, ln1.weight, ln1.bias, ln1.eps, d_h1, f32=f32)
-        yres = tw[0] if f32 else y1
-        rec = dict(x=x, xs=xs, kvs=kvs, qs=qs, c1=c1, lse1=lse1, z1=z1, m1=m1, r1=r1, y1=y1, d_att=d_att, d_h1=d_h1, cross=cross)
-        y2 = y1
-        if cross:
-            d_att2, d_h2 = Fx.drop_params(p_att, _next_seed()), Fx.drop_params(p_hid, _next_seed())
-            q2 = Fx.gemm_nt(y1, s["q2"].wb, s["q2"].b)
+        c1, lse1 = Fx.attn_fwd(qs, kvs[:, :D], kvs[:, D:], B, H, Tq, T, scale, drop=drops[0], q_pack=sel, k_pack=kp, zero_fill=False)
+
+        def cross_fwd(q2):
             kv = pre.take(kv_pair)
-            c2, lse2, c2lo = Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], B, H, Tq, Nenc, scale, drop=d_att2, groups=groups, q_pack=sel, zero_fill=False,
-                                         lo=True)
-            h2 = Fx.gemm_nt(c2, s["o2"].wb, s["o2"].b)
-            ln2 = layer.crossattention.output.LayerNorm
-            y2, z2, m2, r2, *tw = Fx.ln_post_fwd(h2, yres, ln2.weight, ln2.bias, ln2.eps, d_h2, f32=f32)
-            yres = tw[0] if f32 else y2
-            rec.update(q2=q2, kv=kv, c2=c2, c2lo=c2lo, lse2=lse2, z2=z2, m2=m2, r2=r2, y2=y2, d_att2=d_att2, d_h2=d_h2)
-        d_h3 = Fx.drop_params(p_hid, _next_seed())
-        hact, u = Fx.gemm_nt(y2, s["i"].wb, s["i"].b, epi=Fx.EPI_GELU)
-        h3 = Fx.gemm_nt(hact, s["out"].wb, s["out"].b)
-        ln3 = layer.output.LayerNorm
-        y3, z3, m3, r3, *tw = Fx.ln_post_fwd(h3, yres, ln3.weight, ln3.bias, ln3.eps, d_h3, f32=f32)
-        rec.update(hact=hact, u=u, z3=z3, m3=m3, r3=r3, d_h3=d_h3)
+            return (kv,) + Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], B, H, Tq, Nenc, scale, drop=drops[2], groups=groups, q_pack=sel, zero_fill=False,
+                                       lo=True)
+        y3, yres, rec = forward_tail(layer, c1, xres, drops, f32, cross_fwd if cross else None)
+        rec.update(x=x, xs=xs, kvs=kvs, qs=qs, lse1=lse1)
         ctx.rec, ctx.model, ctx.enc, ctx.layer = rec, model, enc, layer
         need_dx = x.requires_grad or (x32 is not None and x32.requires_grad)
         ctx.meta = (B, T, Nenc, scale, groups, kp, rows, sel, Tq, need_dx, enc is not None and enc.requires_grad)
         ctx.noted = need_dx or (enc is not None and enc.requires_grad)
         if ctx.noted:
             arena_note_use(model)
-        return y3, (tw[0] if f32 else None)
+        return y3, (yres if f32 else None)
 
     @staticmethod
     def backward(ctx, dy, dy32=None):
@@ -717,42 +496,24 @@ class _LastLayerRowsFn(torch.autograd.Function):
         B, T, Nenc, scale, groups, kp, rows, sel, Tq, need_dx, need_denc = ctx.meta
         cfg = model.config
         D, H = cfg.hidden_size, cfg.num_attention_heads
-        g, s = grad_view, layer._s
+        s = layer._s
         dy_a, dy_b = _grad_pair(dy, dy32, _F32_STREAM)
         dy = dy_a
         wg = _WgradStream(dy.device, "fusion bwd" if enc is not None else "text bwd")
-        ln3 = layer.output.LayerNorm
-        dh3, dres3 = Fx.ln_post_bwd(dy_a, r["z3"], r["m3"], r["r3"], ln3.weight, g(ln3.weight), g(ln3.bias), s["out"].db, dy2=dy_b,
-                                    drop=r["d_h3"])
-        wg.gemm_tn(dh3, r["hact"], s["out"].dw)
-        du = Fx.gemm_nt(dh3, s["out"].wt, epi=Fx.EPI_DGELU, aux=r["u"], n=s["out"].K)
-        y2 = r["y2"] if r["cross"] else r["y1"]
-        wg.gemm_tn(du, y2, s["i"].dw, dbias=s["i"].db)
-        d1a, d1b = Fx.gemm_nt(du, s["i"].wt, n=s["i"].K), dres3
         denc = None
-        if r["cross"]:
-            ln2 = layer.crossattention.output.LayerNorm
-            dh2, dres2 = Fx.ln_post_bwd(d1a, r["z2"], r["m2"], r["r2"], ln2.weight, g(ln2.weight), g(ln2.bias), s["o2"].db, dy2=d1b,
-                                        drop=r["d_h2"])
-            wg.gemm_tn(dh2, r["c2"], s["o2"].dw)
-            dc2 = Fx.gemm_nt(dh2, s["o2"].wt, n=s["o2"].K)
+
+        def cross_bwd(dc2, r):
             kv = r["kv"]
             dq2 = torch.empty_like(r["q2"])
             dkv = torch.empty((enc.shape[0], 2 * D), dtype=BF16, device=dq2.device)
             args = (dc2, r["q2"], kv[:, :D], kv[:, D:], r["c2"], r["lse2"], dq2, dkv[:, :D], dkv[:, D:], B, H, Tq, Nenc, scale)
-            kw = dict(drop=r["d_att2"], groups=groups, q_pack=sel, o_lo=r["c2lo"])
-            delta = Fx.attn_bwd(*args, phase=1, **kw)
-            wg.run(lambda: Fx.attn_bwd(*args, phase=2, delta=delta, **kw), keep=args[:9] + (delta,))
-            wg.gemm_tn(dq2, r["y1"], s["q2"].dw, dbias=s["q2"].db)
-            wg.gemm_tn(dkv, enc, s["kv2"].dw, dbias=s["kv2"].db)
-            if need_denc:
-                denc = wg.run(lambda: Fx.gemm_nt(dkv, s["kv2"].wt, n=s["kv2"].K), keep=(dkv,))
-            d1a, d1b = Fx.gemm_nt(dq2, s["q2"].wt, n=s["q2"].K), dres2
-        ln1 = layer.attention.output.LayerNorm
-        dh1, dres1 = Fx.ln_post_bwd(d1a, r["z1"], r["m1"], r["r1"], ln1.weight, g(ln1.weight), g(ln1.bias), s["o"].db, dy2=d1b,
-                                    drop=r["d_h1"])
-        wg.gemm_tn(dh1, r["c1"], s["o"].dw)
-        dc1 = Fx.gemm_nt(dh1, s["o"].wt, n=s["o"].K)
+            cross_bwd_split(wg, args, dict(drop=r["d_att2"], groups=groups, q_pack=sel, o_lo=r["c2lo"]))
+            return dq2, dkv
+
+        def set_denc(dkv, r):
+            nonlocal denc
+            denc = wg.run(lambda: Fx.gemm_nt(dkv, s["kv2"].wt, n=s["kv2"].K), keep=(dkv,))
+        dc1, dres1 = backward_tail(layer, r, dy_a, dy_b, wg, enc, cross_bwd, set_denc if need_denc else None)
         kvs, qs = r["kvs"], r["qs"]
         dqs, dkvs = torch.empty_like(qs), torch.empty_like(kvs)
         Fx.attn_bwd(dc1, qs, kvs[:, :D], kvs[:, D:], r["c1"], r["lse1"], dqs, dkvs[:, :D], dkvs[:, D:], B, H, Tq, T, scale, drop=r["d_att"],
