@@ -150,6 +150,17 @@ def grad_of(p):
     return p._xfm_grad
 
 
+def arena_note_use(mod, delta=+1):
+    """A pass that will write `mod`'s parameter gradients has run its forward (+1) / its backward (-1): the owner's use count."""
+    hook = getattr(mod, "_use_hook", None)
+    if hook is not None:
+        hook(mod, delta)
+
+
+def arena_note_grad(mod):
+    arena_note_use(mod, -1)
+
+
 class ParamArena:
     def __init__(self, module, slots=(), device=None):
         params = []

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as Fx
-from .arena import LinearSlot, OwnsArena, ParamArena
+from .arena import LinearSlot, OwnsArena, ParamArena, arena_note_grad, arena_note_use, grad_of
 from .ops import linear_slot
 from .side_stream import _WgradStream
 
@@ -275,7 +275,7 @@ class _TrunkFn(torch.autograd.Function):
             (y, dense, qkv, ctxv, lse, h1, x1, mean2, rstd2, y2, u, hact, h2, x2, meann, rstdn, dp1, dp2, dense_t, ctxv_lo, tiles) = ctx.saved[i]
             final_norm = vit._final_norm if hasattr(vit, "_final_norm") else vit.fc_norm
             nxt = blocks[i + 1].norm1 if i + 1 < len(blocks) else final_norm
-            g = _g
+            g = grad_of
             g1 = blk.gamma_1 if blk.gamma_1 is not None else vit._ones
             g2 = blk.gamma_2 if blk.gamma_2 is not None else vit._ones
             dg1 = g(blk.gamma_1) if blk.gamma_1 is not None else None
@@ -325,7 +325,7 @@ class _TrunkFn(torch.autograd.Function):
                     done = i + 1
         x0, mean0, rstd0 = ctx.first
         n0 = blocks[0].norm1
-        Fx.ln_bwd(dy, x0, mean0, rstd0, n0.weight, _g(n0.weight), _g(n0.bias), dx32=dstream, dx_accum=True)
+        Fx.ln_bwd(dy, x0, mean0, rstd0, n0.weight, grad_of(n0.weight), grad_of(n0.bias), dx32=dstream, dx_accum=True)
         wg.join()
         if dstream.is_cuda:
             ev = torch.cuda.Event()
@@ -385,46 +385,28 @@ class _TokensFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dx0):
-        dmask = _g(ctx.mask_token).view(-1) if ctx.mask is not None else None
-        dtok = Fx.vit_tokens_bwd(dx0.contiguous(), ctx.mask, ctx.Bt, _g(ctx.cls_token).view(-1), dmask)
+        dmask = grad_of(ctx.mask_token).view(-1) if ctx.mask is not None else None
+        dtok = Fx.vit_tokens_bwd(dx0.contiguous(), ctx.mask, ctx.Bt, grad_of(ctx.cls_token).view(-1), dmask)
         return dtok, None, None, None, None
 
 
 # XFM_ATTN_FAST_DELTA=1: the attention backward takes delta = dO . O from the forward's output (kept as bf16 hi + lo halves) instead of a
 # first pass over the keys: dQ kernel 198 -> 165 us, forward 69 -> 80 us at B = 128 (tools/bench_attn.py), the step unchanged within
 # noise (41.6 vs 41.5 ms, tools/ab.sh) -- off by default, the exact two-pass form costs nothing
-_FAST_DELTA = __import__("os").environ.get("XFM_ATTN_FAST_DELTA", "0") != "0"
-_VIT_FUSED_BWD = __import__("os").environ.get("XFM_ATTN_VIT_BWD", "0") != "0"   # opt-in single-pass attention backward (measured slower than the split pair: csrc/attention_vit.hip)
+_FAST_DELTA = os.environ.get("XFM_ATTN_FAST_DELTA", "0") != "0"
+_VIT_FUSED_BWD = os.environ.get("XFM_ATTN_VIT_BWD", "0") != "0"   # opt-in single-pass attention backward (measured slower than the split pair: csrc/attention_vit.hip)
 # the trunk's gradients leave for the all-reduce in chunks of this many blocks, from inside its backward; what is still there when the
 # backward ends (blocks 0 .. chunk, the embeddings) is the exposed tail of the exchange: 2 -> 3 blocks = 85 MB of fp32 gradients behind
 # five overlapped 57-MB collectives (round 2: 4 -> 5 blocks = 142 MB behind two of 114 MB)
 # XFM_VIT_DEFER_WGRAD=0: one xfm_gemm_tn per projection as the backward reaches it (rounds 1-3) instead of the grouped launch
-_DEFER_WGRAD = __import__("os").environ.get("XFM_VIT_DEFER_WGRAD", "1") != "0"
-_RELPOS_AHEAD = __import__("os").environ.get("XFM_VIT_RELPOS_AHEAD", "1") != "0"   # A/B knob: the blocks' dense biases built up front on the second stream
-_DEFER_LN = __import__("os").environ.get("XFM_VIT_DEFER_LN", "1") != "0"   # A/B knob: one batched LayerNorm column-sum reduce for the trunk
-_WGRAD_GROUP_BLOCKS = int(__import__("os").environ.get("XFM_VIT_WGRAD_GROUP", "0"))   # blocks per grouped launch (0: the whole trunk at its end)
+_DEFER_WGRAD = os.environ.get("XFM_VIT_DEFER_WGRAD", "1") != "0"
+_RELPOS_AHEAD = os.environ.get("XFM_VIT_RELPOS_AHEAD", "1") != "0"   # A/B knob: the blocks' dense biases built up front on the second stream
+_DEFER_LN = os.environ.get("XFM_VIT_DEFER_LN", "1") != "0"   # A/B knob: one batched LayerNorm column-sum reduce for the trunk
+_WGRAD_GROUP_BLOCKS = int(os.environ.get("XFM_VIT_WGRAD_GROUP", "0"))   # blocks per grouped launch (0: the whole trunk at its end)
 # (round 4: every hand-over also launches the chunk's queued weight gradients as one grouped call -- 0.43 ms per block in chunks of two,
 # 0.37 in chunks of four, 0.33 for the whole trunk at once -- so chunks of four again: 0.6 ms less weight-gradient time than chunks of
 # two for ~0.25 ms more exposed exchange (blocks 0-4 instead of 0-2 after the backward))
-_GRAD_CHUNK_BLOCKS = max(1, int(__import__("os").environ.get("XFM_VIT_GRAD_CHUNK", "4")))
-
-
-def _g(p):
-    """gradient view of a parameter inside the arena (marks it live; re-attached if a caller dropped .grad)."""
-    from .arena import grad_of
-    return grad_of(p)
-
-
-def arena_note_use(mod):
-    hook = getattr(mod, "_use_hook", None)
-    if hook is not None:
-        hook(mod, +1)
-
-
-def arena_note_grad(mod):
-    hook = getattr(mod, "_use_hook", None)
-    if hook is not None:
-        hook(mod, -1)
+_GRAD_CHUNK_BLOCKS = max(1, int(os.environ.get("XFM_VIT_GRAD_CHUNK", "4")))
 
 
 class VisionTransformer(OwnsArena, nn.Module):

@@ -1,12 +1,29 @@
 """The kernel-by-kernel body of a RobertaLayer behind its self-attention, written once: the forward from the attention output
 projection to the third LayerNorm and the backward from there down to the gradient of the self-attention output.  Callers
-(xroberta._EncoderFn: full rows, xroberta._LastLayerRowsFn: selected rows, decode._run_layers: the cache) bring their own self-attention,
-their cross-attention kernels as closures, and their input-gradient epilogue."""
+(roberta_encoder._EncoderFn: full rows, roberta_encoder._LastLayerRowsFn: selected rows, decode._run_layers: the cache) bring their own
+self-attention, their cross-attention kernels as closures, and their input-gradient epilogue.  Also the towers' dropout seed bookkeeping."""
+import torch
+
 from . import functional as Fx
 from .ops import grad_view
 
 NO_DROPS = (Fx.drop_params(0.0, 0),) * 5
 """The drop tuples of an inference pass (no seed drawn)."""
+
+_seed_counter = [0]   # the towers' dropout seed counter: ONE list, advanced in place by _next_seed and by the native executor
+
+
+def _next_seed():
+    _seed_counter[0] += 1
+    return ((torch.initial_seed() & 0xFFFFFFFF) << 32) | (_seed_counter[0] & 0xFFFFFFFF)
+
+
+def _layer_drops(p_att, p_hid, cross):
+    """A layer's drop tuples (d_att, d_h1, d_att2, d_h2, d_h3), seeds drawn in that order (the two cross entries: None and no seed
+    without cross-attention; the counter advances in eval mode too)."""
+    d_att, d_h1 = Fx.drop_params(p_att, _next_seed()), Fx.drop_params(p_hid, _next_seed())
+    d_att2, d_h2 = (Fx.drop_params(p_att, _next_seed()), Fx.drop_params(p_hid, _next_seed())) if cross else (None, None)
+    return d_att, d_h1, d_att2, d_h2, Fx.drop_params(p_hid, _next_seed())
 
 
 def forward_tail(layer, c1, res, drops, f32, cross=None, save=True):

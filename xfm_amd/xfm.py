@@ -26,6 +26,7 @@ from .arena import LinearSlot, ParamArena
 from . import beit2 as _beit2
 from .beit2 import _Affine, beit_base_patch16
 from .ops import itc_loss, layer_norm, linear_slot, row_normalize, small_ce
+from .roberta_layer import _next_seed
 from .xroberta import RobertaConfig, RobertaForMaskedLM, _Lin, rowwise
 
 BF16 = torch.bfloat16
@@ -499,7 +500,6 @@ class XFMBase(nn.Module):
     def get_hard_negatives(self, image_feat, text_feat, idx=None):
         """Returns device index tensors (image_neg_idx, text_neg_idx), each [B] int64: one kernel -- similarity row, softmax + 1e-5, own
         entry (with `idx`: every entry of the same image id, xfm.py:731-734) zeroed, one inverse-CDF draw per row."""
-        from .xroberta import _next_seed
         temp = self.temp.detach().float().reshape(1) if torch.is_tensor(self.temp) else \
             torch.full((1,), float(self.temp), dtype=torch.float32, device=image_feat.device)
         return Fx.hard_negatives(image_feat.detach().float().contiguous(), text_feat.detach().float().contiguous(), temp, _next_seed(),
