@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 17
+#define XFM_ABI_VERSION 18
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -642,6 +642,47 @@ typedef struct {
   int B;
 } xfm_next_token_args;
 int xfm_next_token(const xfm_next_token_args* a, void* stream);
+
+/* xfm_sample_token (ABI 18): one launch per SAMPLED decoding step -- xbert.py:1422-1462 with do_sample (:1434-1441) and
+ * top_k_top_p_filtering (:1487-1519, min_tokens_to_keep = 1) on the device.  Per row b of the fp32 logits [B, ld] (V <= ld columns count):
+ *   z_j = the repetition-penalised logit of xfm_next_token (once per distinct id of ids[b, :cur_len]) DIVIDED by `temperature` (an IEEE
+ *       fp32 divide, :1437); -inf inputs stay -inf; the logits themselves are not modified.
+ *   top_k > 0: k' = min(max(top_k, 1), V), t = the k'-th largest z counted with multiplicity; every z_j >= t is kept (:1500 removes only
+ *       logits < kth, so equal values at the cut are all kept).  Exact: a radix select over the order-preserving 32-bit image of z.
+ *   top_p < 1, over what top-k kept: the order is descending z, EQUAL VALUES IN ASCENDING COLUMN ORDER (torch.sort leaves that open; this
+ *       is the library's rule); p = softmax over the kept set, c_i its inclusive running sum; position i stays iff i == 0 or
+ *       c_{i-1} <= top_p (:1508-1514).
+ *   draw, over the final kept set: m = max z, w_j = exp(z_j - m), Z = sum w; u = uniforms[b] when uniforms != NULL (fp32 in [0, 1), used
+ *       as given), else u = (r >> 8) 2^-24 with r = rng_u32(rng_row_key(seed_lo, seed_hi, b), step) of csrc/common.h; C_j = the inclusive
+ *       running sum of w over the kept columns in ascending COLUMN order; tok = the lowest kept column with C_j > u Z (if rounding leaves
+ *       none: the highest kept column with w_j > 0).
+ *   lp = z_tok - m - log Z: log_softmax of the filtered row at the token (:1447-1448).
+ *   Sums: every w_j is taken ONCE as the integer floor(2^44 exp(z_j - m)) (fp32 __expf, exact scaling), and every sum of w -- the top-p
+ *       running sum, Z, C_j -- is a 64-bit integer sum (V <= 2^17 terms of at most 2^44).  Integer addition has no order, so no sum
+ *       depends on the order of the lanes, and a running sum carries no rounding beyond the V 2^-44 of the floors (the comparisons
+ *       c_{i-1} <= top_p and C_j > u Z are made on integers against floor(top_p Z) and floor(u Z), both products in fp64).
+ *   The bookkeeping is xfm_next_token's: ids[b, cur_len], hist_unfinished, hist_logprob, the eos update of unfinished, *n_unfinished.
+ *   filtered (may be NULL): fp32 [B, filtered_ld], columns [0, V) receive z_j where kept and -inf elsewhere: top_k_top_p_filtering of the
+ *       penalised, tempered row (a -0 is stored as +0).
+ * A row with no finite z, with a NaN or with +inf gives tok = 0 and lp = NaN (filtered: z unfiltered).  Nothing is read or written out of
+ * range.  No float atomics; the same bits run to run and with and without XFM_DETERMINISTIC.  top_k == 0 and top_p == 1 skip both selects.
+ * XFM_E_ARG (nothing is launched): every case of xfm_next_token; temperature not finite or <= 0; top_p outside (0, 1]; top_k < 0;
+ * filtered != NULL with filtered_ld < V. */
+typedef struct {
+  const float* logits; long ld; int V;
+  int64_t* ids; long ids_ld; int cur_len;
+  float penalty;
+  float temperature; int top_k; float top_p;
+  uint32_t seed_lo, seed_hi;
+  const float* uniforms;                  /* [B] or NULL: the device generator */
+  float* filtered; long filtered_ld;      /* may be NULL */
+  int* unfinished;                        /* [B], 1 / 0 */
+  int* hist_unfinished; float* hist_logprob; long hist_ld; int step;
+  int pad_id; int n_eos; int eos_ids[XFM_NEXT_TOKEN_MAX_EOS];
+  int* n_unfinished;
+  int B;
+} xfm_sample_token_args;
+int xfm_sample_token(const xfm_sample_token_args* a, void* stream);
 
 /* ---- Device Mixup / CutMix (timm Mixup._mix_batch / _mix_elem and mixup_target as called at Imagenet.py:468-469; ABI 10) -------------
  * xfm_mixup: fp32 images [B, C, H, W], B even, mixed IN PLACE: row i against the original row j = B - 1 - i, with the per-row device

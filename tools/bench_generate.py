@@ -12,7 +12,14 @@ encoder states; with them no row emits --eos, so every variant runs all the step
 generation (counted by wrapping xfm_amd.functional's entry points), and how many rows of the two loops part and the largest uncached
 top-1 margin at the step where one does (before it both saw the same prefix, so that margin says whether the parting is a near-tie of the
 16-bit arithmetic).  --only NAME runs one variant alone (for a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/bench_generate.py
---only uncached)."""
+--only uncached).
+
+    python tools/bench_generate.py --sampling [--batch 32] [--samples 5] ...
+
+times SAMPLED generation at the captioning-with-samples shape (32 images x 5 samples = 160 rows over 32 encoder states through
+encoder_batch_index, 577 encoder tokens, max_length 20, 12 layers): fused_sampling on (one xfm_sample_token launch per step) and off
+(the torch sampling lines) alternately in one process, at (top_k, top_p) = (0, 1) and (50, 0.9), temperature 1, no penalty; seven rounds
+after a warm-up, as above.  --only NAME runs one variant alone (for a kernel trace of the sampler: --sampling --only "fused (50")."""
 import argparse
 import json
 import os
@@ -45,7 +52,7 @@ def uncached_greedy(m, prompt, max_length, enc, pad, eos):
 def count_library_calls(fn):
     """Calls into xfm_amd.functional's launching wrappers while fn() runs -> {name: calls}."""
     from xfm_amd import functional as Fx
-    names = ("gemm_nt", "ln_fwd", "ln_post_fwd", "attn_fwd", "decode_attn", "next_token", "embed_ln_fwd")
+    names = ("gemm_nt", "ln_fwd", "ln_post_fwd", "attn_fwd", "decode_attn", "next_token", "sample_token", "embed_ln_fwd")
     counts, saved = {}, {}
     for n in names:
         saved[n] = getattr(Fx, n)
@@ -62,6 +69,50 @@ def count_library_calls(fn):
     return counts
 
 
+def time_rounds(variants, rounds):
+    """Every variant once per round, interleaved; round 0 is warm-up -> {name: [seconds]}."""
+    times = {name: [] for name, _ in variants}
+    for r in range(rounds + 1):
+        for name, fn in variants:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if r > 0:
+                times[name].append(time.perf_counter() - t0)
+    return times
+
+
+def sampling(a, m):
+    """fused_sampling on / off at two filter settings -> the result dict."""
+    B, n, pad = a.batch, a.samples, m.config.pad_token_id
+    rows = B * n
+    enc = (0.7 * torch.randn(B, a.enc_tokens, 768, device="cuda")).to(torch.bfloat16)
+    index = torch.arange(B, device="cuda").repeat_interleave(n)
+    prompt = torch.zeros((rows, 1), dtype=torch.int64, device="cuda")   # <s>
+
+    def run(fused, top_k, top_p):
+        return m._generate_no_beam_search(prompt, 1, a.max_length, True, 1.0, top_k, top_p, 1.0, pad, [a.eos], rows, sync_every=8,
+                                          fused_sampling=fused, encoder_hidden_states=enc, encoder_batch_index=index)
+
+    variants = []
+    for top_k, top_p in ((0, 1.0), (50, 0.9)):
+        for fused in (True, False):
+            variants.append((f"{'fused' if fused else 'torch'} ({top_k}, {top_p})", (lambda f=fused, k=top_k, p=top_p: run(f, k, p))))
+    if a.only:
+        variants = [v for v in variants if v[0].startswith(a.only)]
+    with torch.no_grad():
+        times = time_rounds(variants, a.rounds)
+        calls = {name: count_library_calls(fn) for name, fn in variants}
+    steps = a.max_length - 1
+    return {"mode": "sampling", "shape": {"images": B, "samples": n, "rows": rows, "enc_tokens": a.enc_tokens, "max_length": a.max_length,
+                                          "layers": a.layers, "steps": steps},
+            "rounds": a.rounds,
+            "ms": {k: {"median": 1e3 * statistics.median(v), "min": 1e3 * min(v), "max": 1e3 * max(v)} for k, v in times.items()},
+            "ms_per_step": {k: 1e3 * statistics.median(v) / steps for k, v in times.items()},
+            "library_calls_per_generation": calls}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -73,12 +124,22 @@ def main():
     ap.add_argument("--eos", type=int, default=2)
     ap.add_argument("--only", default=None, help="run the variants whose name starts with this (cached / uncached)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sampling", action="store_true", help="time sampled generation, fused_sampling on and off")
+    ap.add_argument("--samples", type=int, default=5, help="--sampling: samples per image")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate needs the GPU (there is no CPU timing to report)")
     from xfm_amd.xroberta import RobertaConfig, RobertaForCausalLM
     torch.manual_seed(0)
     m = RobertaForCausalLM(RobertaConfig(num_hidden_layers=a.layers, fusion_layer=0, encoder_width=768)).cuda().finalize().eval()
+    if a.sampling:
+        line = json.dumps(sampling(a, m))
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     B, pad = a.batch, m.config.pad_token_id
     enc = (0.7 * torch.randn(B, a.enc_tokens, 768, device="cuda")).to(torch.bfloat16)
     prompt = torch.zeros((B, 1), dtype=torch.int64, device="cuda")   # <s>
@@ -91,16 +152,8 @@ def main():
     variants.append(("uncached loop", lambda: uncached_greedy(m, prompt, a.max_length, enc, pad, a.eos)))
     if a.only:
         variants = [v for v in variants if v[0].startswith(a.only)]
-    times = {name: [] for name, _ in variants}
     with torch.no_grad():
-        for r in range(a.rounds + 1):
-            for name, fn in variants:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                fn()
-                torch.cuda.synchronize()
-                if r > 0:   # round 0 is warm-up
-                    times[name].append(time.perf_counter() - t0)
+        times = time_rounds(variants, a.rounds)
         ids_c, _ = cached(a.sync_every[0])
         ids_u, margins = uncached_greedy(m, prompt, a.max_length, enc, pad, a.eos)
         calls = count_library_calls(lambda: cached(100))

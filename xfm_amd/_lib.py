@@ -13,7 +13,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # XFM_HIP_LIB: A/B a differently built library (kernel experiments); the default is the in-tree build.
 LIB_PATH = os.environ.get("XFM_HIP_LIB") or os.path.join(_HERE, "libxfm_hip.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 c_void_p, c_int, c_long, c_float, c_u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_uint32
 
@@ -133,6 +133,15 @@ class NextTokenArgs(ctypes.Structure):   # xfm_next_token_args
                 ("pad_id", c_int), ("n_eos", c_int), ("eos_ids", c_int * NEXT_TOKEN_MAX_EOS), ("n_unfinished", c_void_p), ("B", c_int)]
 
 
+class SampleTokenArgs(ctypes.Structure):   # xfm_sample_token_args
+    _fields_ = [("logits", c_void_p), ("ld", c_long), ("V", c_int), ("ids", c_void_p), ("ids_ld", c_long), ("cur_len", c_int),
+                ("penalty", c_float), ("temperature", c_float), ("top_k", c_int), ("top_p", c_float),
+                ("seed_lo", c_u32), ("seed_hi", c_u32), ("uniforms", c_void_p),
+                ("filtered", c_void_p), ("filtered_ld", c_long), ("unfinished", c_void_p),
+                ("hist_unfinished", c_void_p), ("hist_logprob", c_void_p), ("hist_ld", c_long), ("step", c_int),
+                ("pad_id", c_int), ("n_eos", c_int), ("eos_ids", c_int * NEXT_TOKEN_MAX_EOS), ("n_unfinished", c_void_p), ("B", c_int)]
+
+
 MIM_SUMS_FLOATS = 3 + 3 * 512   # XFM_MIM_SUMS_FLOATS
 SUMSQ_WORKSPACE_FLOATS = 1024   # XFM_SUMSQ_WORKSPACE_FLOATS
 ANSWER_MAX_A, ANSWER_MAX_K = 8192, 1024   # XFM_ANSWER_MAX_A, XFM_ANSWER_MAX_K
@@ -202,6 +211,7 @@ SIGNATURES = {
     "xfm_box_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p]),
     "xfm_decode_attn": (c_int, [ctypes.POINTER(DecodeAttnArgs), c_void_p]),
     "xfm_next_token": (c_int, [ctypes.POINTER(NextTokenArgs), c_void_p]),
+    "xfm_sample_token": (c_int, [ctypes.POINTER(SampleTokenArgs), c_void_p]),
     "xfm_mixup": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "xfm_mixup_target": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_long, c_void_p]),
     "xfm_region_pool_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

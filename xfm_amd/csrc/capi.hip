@@ -349,6 +349,10 @@ int xfm_next_token(const xfm_next_token_args* a, void* stream) {
   NOTNULL(a, "next_token");
   return xfm_next_token_impl(*a, ST(stream));
 }
+int xfm_sample_token(const xfm_sample_token_args* a, void* stream) {
+  NOTNULL(a, "sample_token");
+  return xfm_sample_token_impl(*a, ST(stream));
+}
 int xfm_mixup(float* x, int B, int C, int H, int W, const float* lam, const int* box, void* stream) {
   XFM_REQUIRE(x && lam && box, "mixup: null operand");
   return xfm_mixup_impl(x, B, C, H, W, lam, box, ST(stream));

@@ -10,6 +10,9 @@
 //                 lowest index among equal maxima (or a pre-drawn token), log_softmax at the token in ce_fwd_kernel's arithmetic, the
 //                 unfinished bookkeeping of xbert.py:1446-1462.  No float atomics: every result is a plain store of one lane, and the count
 //                 of unfinished rows is one integer add per row -- the same bits with and without XFM_DETERMINISTIC.
+//   sample_token  the sampled step (xbert.py:1434-1441 with top_k_top_p_filtering :1487-1519) in one launch: one workgroup of 1024 lanes
+//                 per row; penalty and temperature, top-k and top-p by radix selects, the draw, the score, next_token's bookkeeping.
+//                 All sums are 64-bit integer sums of fixed-point weights (see above the kernel).
 #include "common.h"
 
 constexpr int DECODE_PEN_WORDS = XFM_NEXT_TOKEN_MAX_V / 32;   // LDS bitmap of the ids seen so far
@@ -170,6 +173,21 @@ __device__ __forceinline__ float next_token_value(float x, int j, const uint32_t
   return x;
 }
 
+// The bookkeeping of one row's step (xbert.py:1449-1462), by one lane; A = xfm_next_token_args or xfm_sample_token_args (the same fields).
+template <class A>
+__device__ __forceinline__ void decode_book_step(const A& a, int64_t* ids, int row, long chosen, float lp) {
+  const int unf = a.unfinished[row] != 0 ? 1 : 0;
+  const int64_t add = unf ? (int64_t)chosen : (int64_t)a.pad_id;
+  ids[a.cur_len] = add;
+  a.hist_unfinished[(long)row * a.hist_ld + a.step] = unf;
+  a.hist_logprob[(long)row * a.hist_ld + a.step] = lp;
+  int still = unf;
+  for (int e = 0; e < a.n_eos; ++e) still = (add == (int64_t)a.eos_ids[e]) ? 0 : still;
+  a.unfinished[row] = still;
+  int* const counter = a.n_unfinished;
+  if (still && counter != nullptr) atomicAdd(counter, 1);   // integer: the order of the rows cannot change the sum
+}
+
 __global__ __launch_bounds__(256) void next_token_kernel(const xfm_next_token_args a) {
   __shared__ uint32_t seen_bits[DECODE_PEN_WORDS];
   __shared__ float red[4];
@@ -210,15 +228,7 @@ __global__ __launch_bounds__(256) void next_token_kernel(const xfm_next_token_ar
     if (a.next_token != nullptr) chosen = a.next_token[row];
     float lp = __uint_as_float(0x7FC00000u);   // a pre-drawn token outside [0, V): nothing is read
     if (chosen >= 0 && chosen < V) lp = next_token_value(x[chosen], (int)chosen, seen, a.penalty) - lse;
-    const int unf = a.unfinished[row] != 0 ? 1 : 0;
-    const int64_t add = unf ? (int64_t)chosen : (int64_t)a.pad_id;
-    ids[a.cur_len] = add;
-    a.hist_unfinished[(long)row * a.hist_ld + a.step] = unf;
-    a.hist_logprob[(long)row * a.hist_ld + a.step] = lp;
-    int still = unf;
-    for (int e = 0; e < a.n_eos; ++e) still = (add == (int64_t)a.eos_ids[e]) ? 0 : still;
-    a.unfinished[row] = still;
-    if (still && a.n_unfinished != nullptr) atomicAdd(a.n_unfinished, 1);   // integer: the order of the rows cannot change the sum
+    decode_book_step(a, ids, row, chosen, lp);
   }
 }
 
@@ -232,4 +242,264 @@ int xfm_next_token_impl(const xfm_next_token_args& a, hipStream_t st) {
   XFM_REQUIRE(a.penalty > 0.f, "next_token: repetition penalty %g (need > 0)", (double)a.penalty);
   hipLaunchKernelGGL(next_token_kernel, dim3(a.B), dim3(256), 0, st, a);
   return xfm_check_launch("next_token");
+}
+
+// -------------------------------------------------------------------------------------------------------------------- sample_token
+// One workgroup of 1024 lanes per row; the row (196 KiB at V = 50 265, more than the LDS) stays in global memory / L2 and every pass
+// recomputes z_j = penalised logit / temperature from it (one load, one divide).  Passes over the row:
+//   always      1 maximum (+ the NaN / inf check), 2 the kept weights: Z, the first level of the draw, `filtered`;
+//   top_k > 0   4 more: a radix select (8-bit digits, per-bin COUNTS in LDS) of the k'-th largest 32-bit image of z;
+//   top_p < 1   4 more: a radix select over per-bin MASS of the image where the running softmax mass passes top_p; a cut that falls
+//               inside a run of equal values takes 4 count passes over the columns of that run (lowest columns stay).
+// Weights are integers, w_j = floor(2^44 exp(z_j - m)), and every sum of them a 64-bit integer sum (at most 2^17 * 2^44 = 2^61): LDS
+// integer atomics and wave shuffles in any order give the same bits, and the longest chain of fp32 additions in the kernel is ZERO long
+// -- the error of a running sum is the V floors, below 2^17 * 2^-44 = 2^-27 of Z (Z >= w_max = 1), against the 1e-4 the tests allow.
+// The draw walks the columns in rising order through three levels (64 bins of 2048 columns from pass 2, then 64 bins of 32 and 32
+// single columns read by wave 0 alone).
+constexpr int SAMPLE_LANES = 1024;
+constexpr float SAMPLE_FIX = 17592186044416.f;   // 2^44
+typedef unsigned long long sample_u64;
+
+struct SampleRow {
+  const float* x;
+  const uint32_t* seen;
+  float penalty, temperature;
+  __device__ __forceinline__ float z(int c) const {
+    const float v = next_token_value(x[c], c, seen, penalty) / temperature;
+    return v == 0.f ? 0.f : v;   // -0 -> +0: equal values get equal images
+  }
+};
+// order-preserving 32-bit image of a float (no NaN reaches it) and back
+__device__ __forceinline__ uint32_t sample_key(float z) {
+  const uint32_t u = __float_as_uint(z);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sample_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+__device__ __forceinline__ sample_u64 sample_mass(float z, float m) { return (sample_u64)(__expf(z - m) * SAMPLE_FIX); }
+
+__device__ __forceinline__ sample_u64 wave_sum_u64(sample_u64 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_scan_incl(T v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// The k-th largest key (1 <= k <= the number of members) among the members of the row.  MODE 0: every column, keyed by the image of
+// z.  MODE 1: the columns whose image is `tie`, keyed by V - 1 - column (the k-th LOWEST column of a run of equal values).
+template <int MODE>
+__device__ uint32_t sample_select_count(const SampleRow& r, int V, uint32_t k, uint32_t tie, uint32_t* hist, uint32_t* pick) {
+  const int tid = threadIdx.x;
+  uint32_t prefix = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) hist[tid] = 0u;
+    __syncthreads();
+    for (int c = tid; c < V; c += SAMPLE_LANES) {
+      const uint32_t zk = sample_key(r.z(c));
+      if (MODE == 1 && zk != tie) continue;
+      const uint32_t key = MODE == 0 ? zk : (uint32_t)(V - 1 - c);
+      if (shift == 24 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {   // lane l owns bins 255 - 4 l .. 252 - 4 l: the scan runs from the largest digit down
+      uint32_t h[4], s = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { h[e] = hist[255 - 4 * tid - e]; s += h[e]; }
+      uint32_t run = wave_scan_incl(s, tid) - s;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (run < k && run + h[e] >= k) { pick[0] = (uint32_t)(255 - 4 * tid - e); pick[1] = k - run; }
+        run += h[e];
+      }
+    }
+    __syncthreads();
+    prefix |= pick[0] << shift;
+    k = pick[1];
+  }
+  return prefix;
+}
+
+// Top-p cut over the columns whose image is >= kmin: walking the images downwards, the lowest image whose columns still start at a
+// running mass <= floor(top_p * total).  -> key; pick[1] = the mass above that image, pick[2] = the mass of its columns, pick[3] = the limit.
+__device__ uint32_t sample_select_mass(const SampleRow& r, int V, float m, uint32_t kmin, float top_p, sample_u64* mh, sample_u64* pick) {
+  const int tid = threadIdx.x;
+  uint32_t prefix = 0;
+  sample_u64 above = 0, limit = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) mh[tid] = 0ull;
+    __syncthreads();
+    for (int c = tid; c < V; c += SAMPLE_LANES) {
+      const float z = r.z(c);
+      const uint32_t zk = sample_key(z);
+      if (zk < kmin) continue;
+      if (shift == 24 || (zk >> (shift + 8)) == (prefix >> (shift + 8))) {
+        const sample_u64 w = sample_mass(z, m);
+        if (w != 0ull) atomicAdd(&mh[(zk >> shift) & 255u], w);
+      }
+    }
+    __syncthreads();
+    if (tid < 64) {
+      sample_u64 h[4], s = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { h[e] = mh[255 - 4 * tid - e]; s += h[e]; }
+      const sample_u64 inc = wave_scan_incl(s, tid);
+      if (shift == 24) {   // the total of the first level is the softmax denominator of the top-p stage
+        const sample_u64 total = __shfl(inc, 63, 64);
+        limit = (sample_u64)((double)top_p * (double)total);   // top_p < 1: below the total
+        if (tid == 0) pick[3] = limit;
+      }
+      sample_u64 run = above + inc - s;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {   // exactly one bin: the bins of a level split a mass that straddles the limit
+        if (h[e] != 0ull && run <= limit && run + h[e] > limit) { pick[0] = (sample_u64)(255 - 4 * tid - e); pick[1] = run; pick[2] = h[e]; }
+        run += h[e];
+      }
+    }
+    __syncthreads();
+    prefix |= (uint32_t)pick[0] << shift;
+    above = pick[1];
+    limit = pick[3];
+  }
+  return prefix;
+}
+
+__global__ __launch_bounds__(SAMPLE_LANES) void sample_token_kernel(const xfm_sample_token_args a) {
+  __shared__ uint32_t seen_bits[DECODE_PEN_WORDS];
+  __shared__ sample_u64 mh[256];
+  __shared__ sample_u64 pick64[4];
+  __shared__ sample_u64 draw_bins[64];
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t pick32[2];
+  __shared__ float red[SAMPLE_LANES / 64];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  int64_t* ids = a.ids + (long)row * a.ids_ld;
+  const int V = a.V;
+  const uint32_t* seen = nullptr;
+  if (a.penalty != 1.0f) {
+    const int words = (V + 31) >> 5;
+    for (int w = tid; w < words; w += SAMPLE_LANES) seen_bits[w] = 0u;
+    __syncthreads();
+    for (int t = tid; t < a.cur_len; t += SAMPLE_LANES) {
+      const int64_t id = ids[t];
+      if (id >= 0 && id < V) atomicOr(&seen_bits[id >> 5], 1u << (id & 31));
+    }
+    __syncthreads();
+    seen = seen_bits;
+  }
+  const SampleRow r{a.logits + (long)row * a.ld, seen, a.penalty, a.temperature};
+  float* filtered = a.filtered != nullptr ? a.filtered + (long)row * a.filtered_ld : nullptr;
+
+  // pass 1: the maximum; a NaN or +inf anywhere, or no finite value, ends the row
+  float mx = -INFINITY;
+  int bad = 0;
+  for (int c = tid; c < V; c += SAMPLE_LANES) {
+    const float z = r.z(c);
+    bad |= (z != z) || z == INFINITY;
+    mx = fmaxf(mx, z);
+  }
+  mx = wave_max(mx);
+  if (lane == 0) red[tid >> 6] = mx;
+  bad = __syncthreads_or(bad);
+  float m = red[0];
+#pragma unroll
+  for (int w = 1; w < SAMPLE_LANES / 64; ++w) m = fmaxf(m, red[w]);
+  if (bad || m == -INFINITY) {
+    if (filtered != nullptr)
+      for (int c = tid; c < V; c += SAMPLE_LANES) filtered[c] = r.z(c);
+    if (tid == 0) decode_book_step(a, ids, row, 0L, __uint_as_float(0x7FC00000u));
+    return;
+  }
+
+  // top-k: the image of the k'-th largest value; everything at or above it stays
+  uint32_t kmin = 0u;
+  if (a.top_k > 0 && a.top_k < V) kmin = sample_select_count<0>(r, V, (uint32_t)a.top_k, 0u, hist, pick32);
+  // top-p: images above pkey stay; of the columns AT pkey the lowest ones up to column pcol
+  const bool nucleus = a.top_p < 1.0f;
+  uint32_t pkey = 0u;
+  int pcol = V;
+  if (nucleus) {
+    pkey = sample_select_mass(r, V, m, kmin, a.top_p, mh, pick64);
+    const sample_u64 above = pick64[1], ties = pick64[2], limit = pick64[3];
+    const sample_u64 w = sample_mass(sample_unkey(pkey), m);   // > 0: its bin had mass
+    const sample_u64 n_ties = ties / w, stay = (limit - above) / w + 1ull;   // tie j (from 0) stays iff above + j w <= limit
+    if (stay < n_ties) pcol = V - 1 - (int)sample_select_count<1>(r, V, (uint32_t)stay, pkey, hist, pick32);
+  }
+
+  // pass 2: the kept weights -- their sum per 2048 columns (the first level of the draw) and `filtered`
+  if (tid < 64) draw_bins[tid] = 0ull;
+  __syncthreads();
+  for (int c0 = tid - lane; c0 < V; c0 += SAMPLE_LANES) {   // a wave walks 64 columns of one bin together
+    const int c = c0 + lane;
+    sample_u64 w = 0ull;
+    if (c < V) {
+      const float z = r.z(c);
+      const uint32_t zk = sample_key(z);
+      const bool kept = zk >= kmin && (!nucleus || zk > pkey || (zk == pkey && c <= pcol));
+      if (kept) w = sample_mass(z, m);
+      if (filtered != nullptr) filtered[c] = kept ? z : -INFINITY;
+    }
+    w = wave_sum_u64(w);
+    if (lane == 0 && w != 0ull) atomicAdd(&draw_bins[c0 >> 11], w);
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+
+  // the draw, by wave 0: the lowest kept column whose inclusive running weight exceeds floor(u Z)
+  float u;
+  if (a.uniforms != nullptr) u = a.uniforms[row];
+  else u = (float)(rng_u32(rng_row_key(a.seed_lo, a.seed_hi, (uint32_t)row), (uint32_t)a.step) >> 8) * 5.9604644775390625e-8f;
+  sample_u64 h = draw_bins[lane];
+  sample_u64 inc = wave_scan_incl(h, lane);
+  const sample_u64 Z = __shfl(inc, 63, 64);   // >= 2^44: the maximum is always kept
+  sample_u64 target = (sample_u64)((double)u * (double)Z);
+  if (!(target < Z)) target = Z - 1ull;       // u >= 1 or rounding: the highest kept column with weight
+  int first = __ffsll((unsigned long long)__ballot(inc > target)) - 1;
+  sample_u64 base = __shfl(inc - h, first, 64);
+  // level 2: lane l sums columns [first * 2048 + 32 l, + 32)
+  auto weight = [&](int c) -> sample_u64 {
+    if (c >= V) return 0ull;
+    const float z = r.z(c);
+    const uint32_t zk = sample_key(z);
+    const bool kept = zk >= kmin && (!nucleus || zk > pkey || (zk == pkey && c <= pcol));
+    return kept ? sample_mass(z, m) : 0ull;
+  };
+  h = 0ull;
+  for (int i = 0; i < 32; ++i) h += weight(first * 2048 + lane * 32 + i);
+  inc = base + wave_scan_incl(h, lane);
+  const int second = __ffsll((unsigned long long)__ballot(inc > target)) - 1;
+  base = __shfl(inc - h, second, 64);
+  // level 3: one column per lane
+  const int c3 = first * 2048 + second * 32 + (lane & 31);
+  h = lane < 32 ? weight(c3) : 0ull;
+  inc = base + wave_scan_incl(h, lane);
+  const int third = __ffsll((unsigned long long)__ballot(h != 0ull && inc > target)) - 1;
+  if (tid == 0) {
+    int tok = first * 2048 + second * 32 + third;
+    tok = tok < 0 ? 0 : (tok < V ? tok : V - 1);   // (always inside already: the three ballots cannot come up empty)
+    const float lp = r.z(tok) - m - __logf((float)Z * (1.0f / SAMPLE_FIX));
+    decode_book_step(a, ids, row, (long)tok, lp);
+  }
+}
+
+int xfm_sample_token_impl(const xfm_sample_token_args& a, hipStream_t st) {
+  XFM_REQUIRE(a.logits && a.ids && a.unfinished && a.hist_unfinished && a.hist_logprob, "sample_token: null operand");
+  XFM_REQUIRE(a.B >= 1 && a.V >= 1 && (long)a.V <= a.ld, "sample_token: B=%d V=%d ld=%ld (need B >= 1, 1 <= V <= ld)", a.B, a.V, a.ld);
+  XFM_REQUIRE(a.V <= XFM_NEXT_TOKEN_MAX_V, "sample_token: V = %d exceeds %d", a.V, XFM_NEXT_TOKEN_MAX_V);
+  XFM_REQUIRE(a.cur_len >= 0 && (long)a.cur_len < a.ids_ld, "sample_token: column cur_len = %d is outside the id rows of %ld", a.cur_len, a.ids_ld);
+  XFM_REQUIRE(a.step >= 0 && (long)a.step < a.hist_ld, "sample_token: step %d is outside the history rows of %ld", a.step, a.hist_ld);
+  XFM_REQUIRE(a.n_eos >= 0 && a.n_eos <= XFM_NEXT_TOKEN_MAX_EOS, "sample_token: %d eos ids (at most %d)", a.n_eos, XFM_NEXT_TOKEN_MAX_EOS);
+  XFM_REQUIRE(a.penalty > 0.f, "sample_token: repetition penalty %g (need > 0)", (double)a.penalty);
+  XFM_REQUIRE(a.temperature > 0.f && a.temperature <= 3.402823466e38f, "sample_token: temperature %g (need finite and > 0)", (double)a.temperature);
+  XFM_REQUIRE(a.top_p > 0.f && a.top_p <= 1.f, "sample_token: top_p %g (need 0 < top_p <= 1)", (double)a.top_p);
+  XFM_REQUIRE(a.top_k >= 0, "sample_token: top_k %d (need >= 0)", a.top_k);
+  XFM_REQUIRE(a.filtered == nullptr || a.filtered_ld >= (long)a.V, "sample_token: filtered row stride %ld below V = %d", a.filtered_ld, a.V);
+  hipLaunchKernelGGL(sample_token_kernel, dim3(a.B), dim3(SAMPLE_LANES), 0, st, a);
+  return xfm_check_launch("sample_token");
 }

@@ -10,6 +10,7 @@ What the reference does with `use_cache` / `past_key_values` (models/xroberta.py
     row runs through `Fx.decode_attn` in place of the two `Fx.attn_fwd` calls.
   * `GenerationMixin`: `prepare_inputs_for_generation`, `_reorder_cache`, `_generate_no_beam_search` with the reference's signatures;
     one `Fx.next_token` launch per step does the penalty, the choice, the score and the finished-row bookkeeping on the device.
+    With `do_sample` and `fused_sampling=True` that launch is `Fx.sample_token`, which also filters (top-k / top-p) and draws on the device.
 Inference only: eval mode under torch.no_grad().  Beam search and HF's generate() are not built."""
 import math
 from types import SimpleNamespace
@@ -252,13 +253,18 @@ class GenerationMixin:
 
     @torch.no_grad()
     def _generate_no_beam_search(self, input_ids, cur_len, max_length, do_sample, temperature, top_k, top_p, repetition_penalty,
-                                 pad_token_id, eos_token_ids, batch_size, sync_every=SYNC_EVERY, **model_kwargs):
+                                 pad_token_id, eos_token_ids, batch_size, sync_every=SYNC_EVERY, fused_sampling=False, seed=None, uniforms=None,
+                                 **model_kwargs):
         """xbert.py:1393-1484: greedy (or sampled) decoding without beams -> (input_ids [B, max_length] padded with pad_token_id, the mean
         log-probability of every row's own tokens).  model_kwargs: encoder_hidden_states, encoder_attention_mask, encoder_batch_index
         (extension), past.  Every step is the cached forward of one token and ONE Fx.next_token launch; the host reads nothing inside the
         loop but the unfinished-row counter, every `sync_every` steps (extension).  Where the reference breaks once every row has
         finished, running on changes nothing: finished rows only receive pads and their history entries are masked, so the result does
-        not depend on sync_every."""
+        not depend on sync_every.
+        fused_sampling (extension, default off): with do_sample, the penalty, the temperature, top_k_top_p_filtering, the draw and the
+        score of a step are ONE Fx.sample_token launch on the head's logits in place of the torch ops below.  The draws come from the
+        library's counter generator keyed by `seed` (None: one 64-bit seed per call from torch's CPU generator, so torch.manual_seed
+        makes a call reproducible), or from `uniforms` fp32 [B, steps] in [0, 1), column `step` at that step."""
         unknown = set(model_kwargs) - {"encoder_hidden_states", "encoder_attention_mask", "encoder_batch_index", "past"}
         if unknown:
             raise TypeError(f"_generate_no_beam_search: unsupported model keywords {sorted(unknown)} (the decoder attends to every id it is given)")
@@ -278,13 +284,24 @@ class GenerationMixin:
         logits = torch.empty((B, (V + 63) // 64 * 64), dtype=F32, device=dev)
         past = model_kwargs.get("past", None)
         kw = {k: model_kwargs.get(k, None) for k in ("encoder_hidden_states", "encoder_attention_mask", "encoder_batch_index")}
+        fused = bool(do_sample and fused_sampling)
+        if fused:
+            if uniforms is not None:
+                assert uniforms.shape == (B, steps) and uniforms.dtype == F32, "uniforms: fp32 [batch_size, max_length - cur_len]"
+                uniforms = uniforms.to(dev).t().contiguous()   # row `step` = that step's [B] draws
+            elif seed is None:
+                seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device="cpu"))
         step = 0
         while cur_len < max_length:
             inp = ids[:, :cur_len] if past is None else ids[:, cur_len - 1:cur_len]
             out = tower(inp, past_key_values=past, use_cache=True, is_decoder=True, cache_capacity=max_length, **kw)
             past = out.past_key_values
             head_logits(head, out.last_hidden_state[:, -1, :], out=logits)
-            if do_sample:
+            if fused:
+                Fx.sample_token(logits, V, ids, cur_len, unfinished, hist_u, hist_lp, step, pad_token_id, eos, temperature, top_k, top_p,
+                                0 if seed is None else seed, penalty=repetition_penalty, n_unfinished=counts[step:step + 1],
+                                uniforms=None if uniforms is None else uniforms[step])
+            elif do_sample:
                 lg = logits[:, :V]
                 if repetition_penalty != 1.0:
                     lg = repetition_penalised(lg, ids[:, :cur_len], repetition_penalty)

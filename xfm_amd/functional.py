@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AdamWArgs, AttnArgs, DecodeAttnArgs, EmbedArgs, LnBwdArgs, LnFwdArgs, NextTokenArgs, check
+from ._lib import AdamWArgs, AttnArgs, DecodeAttnArgs, EmbedArgs, LnBwdArgs, LnFwdArgs, NextTokenArgs, SampleTokenArgs, check
 
 BF16, F32 = torch.bfloat16, torch.float32
 EPI_BF16, EPI_F32, EPI_GELU, EPI_DGELU, EPI_F32_ACC = 0, 1, 2, 3, 4
@@ -1091,6 +1091,46 @@ def next_token(logits, V, ids, cur_len, unfinished, hist_unfinished, hist_logpro
         assert n_unfinished.dtype == torch.int32 and n_unfinished.numel() == 1
         a.n_unfinished = n_unfinished.data_ptr()
     check(_lib.load().xfm_next_token(ctypes.byref(a), _stream()), "next_token")
+
+
+def sample_token(logits, V, ids, cur_len, unfinished, hist_unfinished, hist_logprob, step, pad_id, eos_ids, temperature, top_k, top_p, seed,
+                 penalty=1.0, n_unfinished=None, uniforms=None, filtered=None):
+    """xfm_sample_token: one SAMPLED decoding step (xbert.py:1422-1462 with do_sample, top_k_top_p_filtering :1487-1519) in one launch.
+    The operands of next_token, and: temperature > 0, top_k >= 0 (0: off), top_p in (0, 1] (1: off); seed: a 64-bit integer of the device
+    generator (row b at `step` draws from (seed, b, step)); uniforms fp32 [B] in [0, 1): used in place of the generator; filtered fp32
+    [B, >= V] (optional): receives the penalised, tempered, filtered row (-inf where removed)."""
+    for t in (logits, ids, unfinished, hist_unfinished, hist_logprob):
+        _dev(t)
+    B = logits.shape[0]
+    assert logits.dtype == F32 and logits.dim() == 2 and logits.stride(1) == 1 and V <= logits.shape[1]
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[0] == B and ids.stride(1) == 1
+    assert unfinished.dtype == torch.int32 and unfinished.numel() == B and unfinished.is_contiguous()
+    assert hist_unfinished.dtype == torch.int32 and hist_logprob.dtype == F32 and hist_unfinished.shape == hist_logprob.shape
+    assert hist_unfinished.dim() == 2 and hist_unfinished.shape[0] == B and hist_unfinished.is_contiguous() and hist_logprob.is_contiguous()
+    eos = [int(e) for e in eos_ids]
+    assert len(eos) <= _lib.NEXT_TOKEN_MAX_EOS
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a = SampleTokenArgs(logits=logits.data_ptr(), ld=logits.stride(0), V=V, ids=ids.data_ptr(), ids_ld=ids.stride(0), cur_len=int(cur_len),
+                        penalty=float(penalty), temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
+                        seed_lo=seed & 0xFFFFFFFF, seed_hi=seed >> 32, unfinished=unfinished.data_ptr(),
+                        hist_unfinished=hist_unfinished.data_ptr(), hist_logprob=hist_logprob.data_ptr(), hist_ld=hist_unfinished.shape[1],
+                        step=int(step), pad_id=int(pad_id), n_eos=len(eos), B=B)
+    assert 0 <= int(cur_len) < ids.shape[1]
+    for i, e in enumerate(eos):
+        a.eos_ids[i] = e
+    if uniforms is not None:
+        _dev(uniforms)
+        assert uniforms.dtype == F32 and uniforms.numel() == B and uniforms.is_contiguous()
+        a.uniforms = uniforms.data_ptr()
+    if filtered is not None:
+        _dev(filtered)
+        assert filtered.dtype == F32 and filtered.dim() == 2 and filtered.shape[0] == B and filtered.stride(1) == 1 and filtered.shape[1] >= V
+        a.filtered, a.filtered_ld = filtered.data_ptr(), filtered.stride(0)
+    if n_unfinished is not None:
+        _dev(n_unfinished)
+        assert n_unfinished.dtype == torch.int32 and n_unfinished.numel() == 1
+        a.n_unfinished = n_unfinished.data_ptr()
+    check(_lib.load().xfm_sample_token(ctypes.byref(a), _stream()), "sample_token")
 
 
 def mixup_(x, lam, box):
