@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 18
+#define XFM_ABI_VERSION 19
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -584,6 +584,68 @@ int xfm_mse_bwd(const void* pred, long stride, int pred_bf16, const float* targe
  * XFM_E_ARG (nothing is launched): n < 1, R < 1, out_offset < 0, NULL coord / ref_box / ref_size / ref_split / counts. */
 int xfm_box_eval(const float* coord, const int* ref_row, const float* ref_box, const float* ref_size, const int* ref_split, int n, int R,
                  float* out, long out_offset, int64_t* counts, void* stream);
+
+/* ---- Grad-CAM grounding (Grounding.py:76-126 val on the attention-map contract of models/xroberta.py:182-194, 268-270;
+ * dataset/utils.py:178-223 grounding_eval; ABI 19)
+ * xfm_xattn_gradcam: the attention map of ONE cross-attention layer, the gradient that reaches it and their Grad-CAM, in one launch, from
+ * what the layer's backward holds when the gradient dout of its context output arrives.  Eval mode: no attention dropout, no head mask, so
+ *   P[b,h,t,j]  = exp(scale q[b,t,h,:] . k[src(b),j,h,:] - lse[b,h,t])           (the softmax; lse is what xfm_attn_fwd left)
+ *   dP[b,h,t,j] = dout[b,t,h,:] . v[src(b),j,h,:]                                 (the hook's gradient, Grounding.py:104-105)
+ *   cam[b,j-1]  = 1 / (H t_div) sum_h sum_{t < q_len[b]} P[b,h,t,j] max(dP[b,h,t,j], 0),  j = 1 .. Sk - 1     (Grounding.py:109-115)
+ * Both means divide by the full extents: H, and t_div = the padded length T of the batch (not q_len[b]); the sum over t < q_len[b] is the
+ * reference's multiplication by the attention mask; key 0 (the image's [CLS]) is dropped.
+ * Up to three outputs, each may be NULL: cam fp32 [B, Sk - 1]; p_out and dp_out fp32 [B, H, Sq, Sk], rows t >= q_len[b] written as zero
+ * (the reference holds a softmax and an exactly-zero gradient there and multiplies both by the mask).
+ * Operands follow xfm_attn_args addressing: q and dout bf16 token-major, element (row, h, d) at ptr[row * rs + h * 64 + d]; k and v bf16
+ * with their own row strides (the two halves of the layer's K | V projection), key j of source s at row s * Sk + j; lse fp32
+ * [B, H, stat_ld].  Query rows of entry b: q_start[b] .. + q_len[b] (packed), or b * Sq .. + q_len[b] when q_start is NULL (dense); q_len
+ * NULL = Sq rows.  kv_src (optional int [B]): entry b reads key/value source kv_src[b] (NULL: b) of n_src sources -- image_index,
+ * encoder_batch_index and the grouped layout alike; an entry outside [0, n_src) reads nothing and yields zeros.
+ * Head dimension 64; no key mask and no bias (the fusion tower's image keys are never masked on this path).  One workgroup per (entry, 64
+ * keys) walks the heads and sums the query rows in a fixed order: plain vector loads and stores, no atomics, no workspace, the same bits
+ * on every launch, with and without XFM_DETERMINISTIC.
+ * XFM_E_ARG (nothing is launched): cam, p_out and dp_out all NULL; a NULL q / dout / k / v / lse; B < 1, B > 65535, H < 1, Sq < 1, Sk < 2;
+ * a row stride below H * 64 or not a multiple of 8; an operand not 16-byte aligned; stat_ld < Sq or not a multiple of 4; q_start without
+ * q_len; n_src < 1; t_div < 1; scale not positive and finite.  XFM_E_UNSUPPORTED (nothing is launched): Sq > 64, the grouped kernels'
+ * limit. */
+typedef struct {
+  const xfm_bf16* q; long q_rs;
+  const xfm_bf16* dout; long do_rs;
+  const xfm_bf16* k; long k_rs;
+  const xfm_bf16* v; long v_rs;
+  const float* lse; long stat_ld;
+  const int* q_start; const int* q_len;
+  const int* kv_src; int n_src;
+  int B, H, Sq, Sk;
+  float scale; int t_div;
+  float* cam; float* p_out; float* dp_out;
+} xfm_gradcam_args;
+int xfm_xattn_gradcam(const xfm_gradcam_args* a, void* stream);
+
+/* xfm_cam_box_rank: the loop body of grounding_eval (utils.py:183-216) for n refs, one workgroup per ref.  cam fp32 [n, p, p] (row = y);
+ * img_hw int [n, 2] = (height, width) of each ref's image; det fp64 [Ndet, 4] = the detector boxes (x, y, w, h) in pixels, those of ref i
+ * at rows det_start[i] .. det_start[i + 1] (CSR, int [n + 1]); max_dets = the largest number of boxes of one ref (the host knows it: the
+ * boxes come from there); ref_box fp64 [n, 4]; ref_split int [n] = 0 val, 1 testA, 2 testB (anything else: counted nowhere).
+ * The reference upsamples the map to (height, width) with F.interpolate(mode='bicubic') -- align_corners=False, no antialias, A = -0.75 --
+ * and sums it over rows int(y) : int(y + h), columns int(x) : int(x + w) (Python truncation; the slice clamps at the border, and may be
+ * empty).  The upsampled map is never built: the sum is a^T cam b, a_i = the sum over the box's rows of the weight output row y gives
+ * input row i, b_j the same over its columns.  The tap weights are ATen's, in fp32 and in its operation order: source coordinate
+ * (dst + 0.5) * (in / out) - 0.5, tap index floor(src) - 1 .. + 2 clamped to the map, lambda clamped to [0, 1]; a, b and the product are
+ * fp64, and so are area ** alpha (area = w * h) and the comparison.  The chosen box is the first whose score is strictly greater than
+ * every earlier one, starting from 0; its IoU with ref_box is computeIoU (utils.py:349-361), the arithmetic of xfm_box_eval.
+ * out fp64 [N, 3]: row out_offset + i = (index of the chosen box among the ref's own, its score, its IoU); the rows of a whole pass
+ * collect in ONE device buffer.  counts int64 [3, 2]: counts[s] += (#IoU >= 0.5, #refs) of split s, by one workgroup with plain loads
+ * and stores; it ACCUMULATES across calls.  No atomics on global memory: the same bits with and without XFM_DETERMINISTIC.
+ * Defined differently from the reference ON PURPOSE: a ref none of whose boxes scores above 0 gets (-1, 0, 0) and is counted as WRONG; the
+ * reference would reuse the box chosen for the previous ref, or raise on the first one.
+ * Boxes with a negative coordinate are the host's to reject (Python's negative slice bounds mean something else); here they are clamped
+ * to 0, so nothing is read out of bounds.
+ * XFM_E_ARG (nothing is launched): n < 1, p < 1, out_offset < 0, max_dets < 0, alpha not finite, a NULL operand.  XFM_E_UNSUPPORTED
+ * (nothing is launched): p > XFM_CAM_MAX_P or max_dets > XFM_CAM_MAX_DETS, the caps of the LDS layout. */
+#define XFM_CAM_MAX_P 32
+#define XFM_CAM_MAX_DETS 256
+int xfm_cam_box_rank(const float* cam, int p, const int* img_hw, const double* det, const int* det_start, int max_dets, const double* ref_box,
+                     const int* ref_split, int n, double alpha, double* out, long out_offset, int64_t* counts, void* stream);
 
 /* ---- Incremental decoding (models/xbert.py:1368-1484 prepare_inputs_for_generation / _generate_no_beam_search; the cached branches of the
  * attention at models/xroberta.py:224-262; ABI 17)

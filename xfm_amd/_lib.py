@@ -13,7 +13,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # XFM_HIP_LIB: A/B a differently built library (kernel experiments); the default is the in-tree build.
 LIB_PATH = os.environ.get("XFM_HIP_LIB") or os.path.join(_HERE, "libxfm_hip.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 c_void_p, c_int, c_long, c_float, c_u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_uint32
 
@@ -142,6 +142,14 @@ class SampleTokenArgs(ctypes.Structure):   # xfm_sample_token_args
                 ("pad_id", c_int), ("n_eos", c_int), ("eos_ids", c_int * NEXT_TOKEN_MAX_EOS), ("n_unfinished", c_void_p), ("B", c_int)]
 
 
+class GradcamArgs(ctypes.Structure):   # xfm_gradcam_args
+    _fields_ = [("q", c_void_p), ("q_rs", c_long), ("dout", c_void_p), ("do_rs", c_long), ("k", c_void_p), ("k_rs", c_long),
+                ("v", c_void_p), ("v_rs", c_long), ("lse", c_void_p), ("stat_ld", c_long), ("q_start", c_void_p), ("q_len", c_void_p),
+                ("kv_src", c_void_p), ("n_src", c_int), ("B", c_int), ("H", c_int), ("Sq", c_int), ("Sk", c_int),
+                ("scale", c_float), ("t_div", c_int), ("cam", c_void_p), ("p_out", c_void_p), ("dp_out", c_void_p)]
+
+
+CAM_MAX_P, CAM_MAX_DETS = 32, 256   # XFM_CAM_MAX_P, XFM_CAM_MAX_DETS
 MIM_SUMS_FLOATS = 3 + 3 * 512   # XFM_MIM_SUMS_FLOATS
 SUMSQ_WORKSPACE_FLOATS = 1024   # XFM_SUMSQ_WORKSPACE_FLOATS
 ANSWER_MAX_A, ANSWER_MAX_K = 8192, 1024   # XFM_ANSWER_MAX_A, XFM_ANSWER_MAX_K
@@ -209,6 +217,9 @@ SIGNATURES = {
     "xfm_mse_fwd": (c_int, [c_void_p, c_long, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "xfm_mse_bwd": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "xfm_box_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p]),
+    "xfm_xattn_gradcam": (c_int, [ctypes.POINTER(GradcamArgs), c_void_p]),
+    "xfm_cam_box_rank": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p,
+                                 c_long, c_void_p, c_void_p]),
     "xfm_decode_attn": (c_int, [ctypes.POINTER(DecodeAttnArgs), c_void_p]),
     "xfm_next_token": (c_int, [ctypes.POINTER(NextTokenArgs), c_void_p]),
     "xfm_sample_token": (c_int, [ctypes.POINTER(SampleTokenArgs), c_void_p]),

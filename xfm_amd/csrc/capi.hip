@@ -46,6 +46,7 @@ int xfm_cu_count() {
 #include "answer_rank.hip"
 #include "metrics.hip"
 #include "grounding.hip"
+#include "gradcam.hip"
 #include "decode.hip"
 #include "dp.hip"
 
@@ -336,6 +337,14 @@ int xfm_mse_fwd(const void* pred, long stride, int pred_bf16, const float* targe
 }
 int xfm_mse_bwd(const void* pred, long stride, int pred_bf16, const float* target, const float* dloss, int B, float* dpred, void* stream) {
   return xfm_mse_bwd_impl(pred, stride, pred_bf16, target, dloss, B, dpred, ST(stream));
+}
+int xfm_xattn_gradcam(const xfm_gradcam_args* a, void* stream) {
+  NOTNULL(a, "xattn_gradcam");
+  return xfm_xattn_gradcam_impl(a, ST(stream));
+}
+int xfm_cam_box_rank(const float* cam, int p, const int* img_hw, const double* det, const int* det_start, int max_dets, const double* ref_box,
+                     const int* ref_split, int n, double alpha, double* out, long out_offset, int64_t* counts, void* stream) {
+  return xfm_cam_box_rank_impl(cam, p, img_hw, det, det_start, max_dets, ref_box, ref_split, n, alpha, out, out_offset, counts, ST(stream));
 }
 int xfm_box_eval(const float* coord, const int* ref_row, const float* ref_box, const float* ref_size, const int* ref_split, int n, int R,
                  float* out, long out_offset, int64_t* counts, void* stream) {

@@ -1018,6 +1018,62 @@ def box_eval(coord, ref_row, ref_box, ref_size, ref_split, counts, out=None, out
     return counts
 
 
+def xattn_gradcam(q, dout, k, v, lse, B, H, Sq, Sk, scale, t_div, q_pack=None, q_len=None, kv_src=None, n_src=None, cam=True, p_out=False,
+                  dp_out=False):
+    """xfm_xattn_gradcam: q / dout [rows, >= H*64], k / v [n_src * Sk, >= H*64] bf16 2-D (possibly strided column slices), lse fp32
+    [B, H, stat_ld] as attn_fwd left it.  q_pack = (start, len) int32 [B] for packed rows, or q_len int32 [B] alone for dense rows with
+    padding; kv_src int32 [B] names each entry's key/value source.  Returns (cam fp32 [B, Sk - 1] | None, P | None, dP | None), the maps
+    fp32 [B, H, Sq, Sk] with rows past an entry's length zero.  Sq > 64 raises (XFM_E_UNSUPPORTED): gradcam.attention_gradcam falls back."""
+    for t in (q, dout, k, v):
+        _dev(t)
+        assert t.dtype == BF16 and t.dim() == 2 and t.stride(1) == 1
+    _dev(lse)
+    assert lse.dtype == F32 and lse.is_contiguous() and lse.shape[:2] == (B, H)
+    if q_pack is not None:
+        q_start, q_len = q_pack
+    else:
+        q_start = None
+    for t in (q_start, q_len, kv_src):
+        if t is not None:
+            _dev(t)
+            assert t.dtype == torch.int32 and t.numel() == B and t.is_contiguous()
+    if n_src is None:
+        n_src = k.shape[0] // Sk
+    assert k.shape[0] >= n_src * Sk and v.shape[0] >= n_src * Sk and (kv_src is not None or n_src >= B)
+    assert q_start is not None or (q.shape[0] >= B * Sq and dout.shape[0] >= B * Sq)
+    dev = q.device
+    cam_t = torch.empty((B, Sk - 1), dtype=F32, device=dev) if cam else None
+    p_t = torch.empty((B, H, Sq, Sk), dtype=F32, device=dev) if p_out else None
+    dp_t = torch.empty((B, H, Sq, Sk), dtype=F32, device=dev) if dp_out else None
+    a = _lib.GradcamArgs(q=q.data_ptr(), q_rs=q.stride(0), dout=dout.data_ptr(), do_rs=dout.stride(0), k=k.data_ptr(), k_rs=k.stride(0),
+                         v=v.data_ptr(), v_rs=v.stride(0), lse=lse.data_ptr(), stat_ld=lse.shape[-1], q_start=_ptr(q_start), q_len=_ptr(q_len),
+                         kv_src=_ptr(kv_src), n_src=n_src, B=B, H=H, Sq=Sq, Sk=Sk, scale=scale, t_div=int(t_div),
+                         cam=_ptr(cam_t), p_out=_ptr(p_t), dp_out=_ptr(dp_t))
+    check(_lib.load().xfm_xattn_gradcam(ctypes.byref(a), _stream()), "xattn_gradcam")
+    return cam_t, p_t, dp_t
+
+
+def cam_box_rank(cam, img_hw, det, det_start, max_dets, ref_box, ref_split, alpha, counts, out, out_offset=0):
+    """xfm_cam_box_rank: cam fp32 [n, p, p]; img_hw int32 [n, 2] = (height, width); det fp64 [Ndet, 4] (x, y, w, h) with the boxes of ref i
+    at rows det_start[i] .. det_start[i + 1] (int32 [n + 1]); max_dets = the largest count of one ref (a host number); ref_box fp64 [n, 4];
+    ref_split int32 [n].  out fp64 [N, 3]: row out_offset + i = (chosen index or -1, score, IoU); counts int64 [3, 2] += (#IoU >= 0.5,
+    #refs) per split.  p > 32 or max_dets > 256 raises (XFM_E_UNSUPPORTED): gradcam.grounding_eval falls back."""
+    for t in (cam, img_hw, det, det_start, ref_box, ref_split, counts, out):
+        _dev(t)
+        assert t.is_contiguous()
+    n, p = cam.shape[0], cam.shape[1]
+    assert cam.dtype == F32 and cam.shape == (n, p, p)
+    assert img_hw.dtype == torch.int32 and img_hw.shape == (n, 2) and det_start.dtype == torch.int32 and det_start.numel() == n + 1
+    assert det.dtype == torch.float64 and det.dim() == 2 and det.shape[1] == 4
+    assert ref_box.dtype == torch.float64 and ref_box.shape == (n, 4) and ref_split.dtype == torch.int32 and ref_split.numel() == n
+    assert counts.dtype == torch.int64 and counts.numel() == 6
+    assert out.dtype == torch.float64 and out.dim() == 2 and out.shape[1] == 3 and (out_offset < 0 or out_offset + n <= out.shape[0])
+    check(_lib.load().xfm_cam_box_rank(cam.data_ptr(), p, img_hw.data_ptr(), det.data_ptr(), det_start.data_ptr(), int(max_dets),
+                                       ref_box.data_ptr(), ref_split.data_ptr(), n, float(alpha), out.data_ptr(), int(out_offset),
+                                       counts.data_ptr(), _stream()), "cam_box_rank")
+    return out
+
+
 def decode_attn(q, k_cache, v_cache, cap, H, scale, k_new=None, v_new=None, pos=0, Sk=None, key_keep=None, kv_index=None, out=None):
     """xfm_decode_attn: one new query token per batch row against a token-major key/value cache (xroberta.py:224-262 with a past).
     q [B, >= H*64] bf16 (a column slice of the QKV GEMM output will do); k_cache / v_cache: 2-D bf16 views [entries * cap, >= H*64] of the

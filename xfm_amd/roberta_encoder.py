@@ -98,6 +98,34 @@ def _input_grads(dy_a, dy_b, need_dx, twin_in, rows_full):
     return dx, dx32
 
 
+def layer_saves_maps(layer):
+    """Whether `layer`'s cross-attention was asked for its attention maps (RobertaSelfAttention.save_attention)."""
+    return layer.has_cross_attention and layer.crossattention.self.save_attention
+
+
+def save_layer_maps(layer, r, dc2, B, H, T, Nenc, scale, key_keep, pack, xq, enc_keep, enc_index, n_src, p_att):
+    """The attention-map contract for one cross-attention layer from its record r (q2, kv, lse2): dc2 None = after the forward, the
+    probabilities go to save_attention_map; dc2 = the gradient of the context output, dP = dc2 . V^T goes to save_attn_gradients.
+    Both fp32 [B, H, T, Nenc], rows past a sequence's length zero (the lengths are the pack's, or the row sums of a prefix mask).
+    Eval mode only; no key mask on the image keys; xfm_xattn_gradcam for T <= 64, the torch restatement above that."""
+    from .gradcam import attention_gradcam
+    if p_att > 0.0:
+        raise RuntimeError("save_attention: the attention maps are defined in eval mode only (attention dropout is on)")
+    if xq is not None or enc_keep is not None:
+        raise NotImplementedError("save_attention: per-image row ranges and masked image keys are outside the map contract")
+    q_pack = None if pack is None else pack.pair
+    q_len = key_keep.sum(dim=1).to(torch.int32) if (pack is None and key_keep is not None) else None
+    D = H * 64
+    kv = r["kv"]
+    _, P, dP = attention_gradcam(r["q2"], r["q2"] if dc2 is None else dc2, kv[:, :D], kv[:, D:], r["lse2"], B, H, T, Nenc, scale, T,
+                                 q_pack=q_pack, q_len=q_len, kv_src=enc_index, n_src=n_src, cam=False, p_out=dc2 is None, dp_out=dc2 is not None)
+    att = layer.crossattention.self
+    if dc2 is None:
+        att.save_attention_map(P)
+    else:
+        att.save_attn_gradients(dP)
+
+
 class _EncoderFn(torch.autograd.Function):
     """Layers [lo, hi) of a RobertaEncoder.  x: bf16 [B*T, D]; x32: its fp32 twin or None; enc: bf16 [B*N, D] or None.
     -> (y bf16, y fp32 twin or None): see xroberta._F32_STREAM (here the argument `f32`)."""
@@ -153,6 +181,9 @@ class _EncoderFn(torch.autograd.Function):
                     return (kv,) + Fx.attn_fwd(q2, kv[:, :D], kv[:, D:], B, H, T, Nenc, scale, key_keep=enc_keep, drop=d_att2, kv_index=enc_index) + (None,)
             y3, yres, rec = forward_tail(layer, c1, xres, drops, f32, cross)
             rec.update(x=x, qkv=qkv, lse1=lse1, layer=layer)
+            if cross is not None and layer_saves_maps(layer):
+                rec["maps"] = True
+                save_layer_maps(layer, rec, None, B, H, T, Nenc, scale, key_keep, pack, xq, enc_keep, enc_index, enc.shape[0] // Nenc, p_att)
             saved.append(rec)
             x, xres = y3, yres
         ctx.saved, ctx.model, ctx.enc, ctx.f32 = saved, model, enc, f32
@@ -197,6 +228,8 @@ class _EncoderFn(torch.autograd.Function):
 
         def cross_bwd(dc2, r):
             kv = r["kv"]
+            if r.get("maps"):
+                save_layer_maps(r["layer"], r, dc2, B, H, T, Nenc, scale, key_keep, pack, xq, enc_keep, enc_index, enc.shape[0] // Nenc, 0.0)
             dq2 = new_grad(r["q2"])
             if per_image:  # dK/dV accumulated over each image's rows in registers, written once per image
                 dkv = eg.dkv_of(r["layer"])

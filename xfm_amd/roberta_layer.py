@@ -59,35 +59,44 @@ def forward_tail(layer, c1, res, drops, f32, cross=None, save=True):
     return y3, (tw[0] if f32 else y3), rec
 
 
-def backward_tail(layer, r, dy_a, dy_b, wg, enc=None, cross_bwd=None, after_kv2=None):
+def backward_tail(layer, r, dy_a, dy_b, wg, enc=None, cross_bwd=None, after_kv2=None, param_grads=True):
     """Backward of forward_tail -> (dc1, dres1): the gradient of the self-attention output and of the first residual operand.
     (dy_a bf16, dy_b) are the two gradient edges of the layer output; every weight gradient goes through wg.gemm_tn.
     cross_bwd: (dc2, r) -> (dq2, dkv), the caller's cross-attention backward; enc: the image states its K|V were projected from;
-    after_kv2(dkv, r), if given, runs right behind the K|V weight gradient (the caller's gradient of the image states)."""
-    g, s = grad_view, layer._s
+    after_kv2(dkv, r), if given, runs right behind the K|V weight gradient (the caller's gradient of the image states).
+    param_grads=False (gradcam.cross_attention_gradcam: the activation-gradient chain alone): no LayerNorm or bias gradient is
+    accumulated -- the caller's `wg` drops the weight gradients -- and a cross_bwd that returns (None, None) ends the layer's backward
+    there (it wanted dc2 only): -> (None, None)."""
+    s = layer._s
+    g = grad_view if param_grads else (lambda p: None)
+    # (slot.dw / slot.db mark their parameters as live in the gradient arena: not even asked for without param_grads)
+    dw = (lambda name: s[name].dw) if param_grads else (lambda name: None)
+    db = (lambda name: s[name].db) if param_grads else (lambda name: None)
     ln3 = layer.output.LayerNorm
-    dh3, dres3 = Fx.ln_post_bwd(dy_a, r["z3"], r["m3"], r["r3"], ln3.weight, g(ln3.weight), g(ln3.bias), s["out"].db,
+    dh3, dres3 = Fx.ln_post_bwd(dy_a, r["z3"], r["m3"], r["r3"], ln3.weight, g(ln3.weight), g(ln3.bias), db("out"),
                                 dy2=dy_b, drop=r["d_h3"])
-    wg.gemm_tn(dh3, r["hact"], s["out"].dw)
+    wg.gemm_tn(dh3, r["hact"], dw("out"))
     du = Fx.gemm_nt(dh3, s["out"].wt, epi=Fx.EPI_DGELU, aux=r["u"], n=s["out"].K)
-    wg.gemm_tn(du, r["y2"] if r["cross"] else r["y1"], s["i"].dw, dbias=s["i"].db)
+    wg.gemm_tn(du, r["y2"] if r["cross"] else r["y1"], dw("i"), dbias=db("i"))
     d1a, d1b = Fx.gemm_nt(du, s["i"].wt, n=s["i"].K), dres3
     if r["cross"]:
         ln2 = layer.crossattention.output.LayerNorm
-        dh2, dres2 = Fx.ln_post_bwd(d1a, r["z2"], r["m2"], r["r2"], ln2.weight, g(ln2.weight), g(ln2.bias), s["o2"].db,
+        dh2, dres2 = Fx.ln_post_bwd(d1a, r["z2"], r["m2"], r["r2"], ln2.weight, g(ln2.weight), g(ln2.bias), db("o2"),
                                     dy2=d1b, drop=r["d_h2"])
-        wg.gemm_tn(dh2, r["c2"], s["o2"].dw)
+        wg.gemm_tn(dh2, r["c2"], dw("o2"))
         dc2 = Fx.gemm_nt(dh2, s["o2"].wt, n=s["o2"].K)
         dq2, dkv = cross_bwd(dc2, r)
-        wg.gemm_tn(dq2, r["y1"], s["q2"].dw, dbias=s["q2"].db)
-        wg.gemm_tn(dkv, enc, s["kv2"].dw, dbias=s["kv2"].db)
+        if dq2 is None:
+            return None, None
+        wg.gemm_tn(dq2, r["y1"], dw("q2"), dbias=db("q2"))
+        wg.gemm_tn(dkv, enc, dw("kv2"), dbias=db("kv2"))
         if after_kv2 is not None:
             after_kv2(dkv, r)
         d1a, d1b = Fx.gemm_nt(dq2, s["q2"].wt, n=s["q2"].K), dres2
     ln1 = layer.attention.output.LayerNorm
-    dh1, dres1 = Fx.ln_post_bwd(d1a, r["z1"], r["m1"], r["r1"], ln1.weight, g(ln1.weight), g(ln1.bias), s["o"].db,
+    dh1, dres1 = Fx.ln_post_bwd(d1a, r["z1"], r["m1"], r["r1"], ln1.weight, g(ln1.weight), g(ln1.bias), db("o"),
                                 dy2=d1b, drop=r["d_h1"])
-    wg.gemm_tn(dh1, r["c1"], s["o"].dw)
+    wg.gemm_tn(dh1, r["c1"], dw("o"))
     return Fx.gemm_nt(dh1, s["o"].wt, n=s["o"].K), dres1
 
 

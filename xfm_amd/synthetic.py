@@ -353,3 +353,23 @@ def grounding_refs(num_refs, seed=1234, first_ref_id=0):
               ref_size=torch.from_numpy(np.stack([W, H], axis=1).astype(np.float32)),
               ref_split=torch.from_numpy((np.arange(num_refs) % 3).astype(np.int32)),
               ref_index={first_ref_id + r: r for r in range(num_refs)})
+
+
+def grounding_dets(refs, seed=1234, min_boxes=3, max_boxes=8):
+    """The detector boxes the mask-based grounding evaluation ranks (dets[str(image_id)] of dataset/utils.py:195), one fp64 [k, 4] array of
+    (x, y, w, h) per row of `refs` (grounding_refs), k in [min_boxes, max_boxes]: box 0 is the ground-truth box moved by a few pixels (a
+    detector usually proposes the object), the others are formula boxes inside the image; fractional coordinates, as detector output is."""
+    size = refs.ref_size.double().numpy()
+    box = refs.ref_box.double().numpy()
+    R = size.shape[0]
+    count = min_boxes + (uniform01("grounding.dets.count", R, seed) * (max_boxes - min_boxes + 1)).astype(np.int64).clip(0, max_boxes - min_boxes)
+    u = uniform01("grounding.dets", R * max_boxes * 4, seed).reshape(R, max_boxes, 4)
+    out = []
+    for r in range(R):
+        W, H = size[r]
+        w, h = 8.0 + u[r, :, 2] * 0.5 * W, 8.0 + u[r, :, 3] * 0.5 * H
+        x, y = u[r, :, 0] * (W - w), u[r, :, 1] * (H - h)
+        d = np.stack([x, y, w, h], axis=1)[:count[r]]
+        d[0] = (min(box[r, 0] + 1.5, W - 1.0), min(box[r, 1] + 0.75, H - 1.0), box[r, 2], box[r, 3])
+        out.append(np.ascontiguousarray(d, dtype=np.float64))
+    return out

@@ -19,7 +19,7 @@ from .arena import LinearSlot, OwnsArena, ParamArena, arena_note_grad, arena_not
 from .beit2 import _Affine
 from .decode import GenerationMixin, cached_forward
 from .ops import grad_view, lm_head_ce, lm_head_logits
-from .roberta_encoder import _EncoderFn, _LastLayerRowsFn
+from .roberta_encoder import _EncoderFn, _LastLayerRowsFn, layer_saves_maps
 from .roberta_layer import _next_seed, _seed_counter  # noqa: F401  (_seed_counter: THE list the executors advance, written as XR._seed_counter[0])
 from .roberta_native import _KV_AHEAD, _RL_DEFER_LN, _RL_DEFER_WGRAD, _EncoderFnNative  # noqa: F401  (the knobs' defaults are read here)
 from .side_stream import _WgradStream
@@ -163,6 +163,25 @@ class RobertaSelfAttention(nn.Module):
         self.query = _Lin(config.hidden_size, config.hidden_size, std)
         self.key = _Lin(kv_in, config.hidden_size, std)
         self.value = _Lin(kv_in, config.hidden_size, std)
+        # The attention-map contract of the reference's cross-attention (xroberta.py:182-194, 268-270), on cross-attention layers only and
+        # in eval mode only: with save_attention = True the layer's pass runs kernel by kernel on every query row, the forward leaves
+        # softmax(scores) and a backward the gradient that reaches it, both fp32 [B, H, T, Sk] with the rows past a sequence's length zero
+        # (roberta_encoder.save_layer_maps; the fused attention itself never materialises a probability).
+        self.save_attention = False
+        self.attention_map = None
+        self.attn_gradients = None
+
+    def save_attn_gradients(self, attn_gradients):
+        self.attn_gradients = attn_gradients
+
+    def get_attn_gradients(self):
+        return self.attn_gradients
+
+    def save_attention_map(self, attention_map):
+        self.attention_map = attention_map
+
+    def get_attention_map(self):
+        return self.attention_map
 
 
 class RobertaSelfOutput(nn.Module):
@@ -350,10 +369,20 @@ class RobertaModel(nn.Module):
                       encoder_row_ranges[1].to(device=dev, dtype=torch.int32).contiguous(), int(encoder_row_ranges[2]))
             native = _NATIVE_LAYERS and y.is_cuda and (enc is None or xq is not None or
                                                        (encoder_batch_index is not None and Fx.attn_grouped_ok(T, Nenc)))
-            fn = _EncoderFnNative if native else _EncoderFn
+            saving = enc is not None and any(layer_saves_maps(self.encoder.layer[li]) for li in range(lo, hi))
+            fn = _EncoderFn if saving else (_EncoderFnNative if native else _EncoderFn)   # (a layer that saves its maps runs kernel by kernel)
             if output_rows is not None:
                 assert pack is not None and xq is None and grad_batch is None and not is_decoder and key_keep is None
                 assert enc is None or (encoder_batch_index is not None and Fx.attn_grouped_ok(int(output_rows[3]), Nenc))
+                if saving and layer_saves_maps(self.encoder.layer[hi - 1]):
+                    # the last layer saves its maps, so it runs all its query rows: the rows somebody reads are gathered from its output
+                    from .packing import rows_gather
+                    y, y32 = fn.apply(y, y32, enc, self, key_keep, enc_keep, lo, hi, bool(is_decoder), B, T, Nenc, self.training,
+                                      encoder_batch_index, grad_batch, pack, xq, f32)
+                    rows = output_rows[0].to(torch.int32).contiguous()
+                    y, y32 = rows_gather(y, rows), (None if y32 is None else rows_gather(y32, rows))
+                    return SimpleNamespace(last_hidden_state=with_twin(y, y32), pooler_output=None, past_key_values=None,
+                                           hidden_states=None, attentions=None, cross_attentions=None)
                 hi -= 1
             if hi > lo:
                 y, y32 = fn.apply(y, y32, enc, self, key_keep, enc_keep, lo, hi, bool(is_decoder), B, T, Nenc, self.training,
