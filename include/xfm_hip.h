@@ -28,7 +28,7 @@ extern "C" {
 #define XFM_E_LAUNCH (-2)
 #define XFM_E_UNSUPPORTED (-3)
 
-#define XFM_ABI_VERSION 19
+#define XFM_ABI_VERSION 20
 
 const char* xfm_last_error(void);
 int xfm_abi_version(void);
@@ -646,6 +646,27 @@ int xfm_xattn_gradcam(const xfm_gradcam_args* a, void* stream);
 #define XFM_CAM_MAX_DETS 256
 int xfm_cam_box_rank(const float* cam, int p, const int* img_hw, const double* det, const int* det_start, int max_dets, const double* ref_box,
                      const int* ref_split, int n, double alpha, double* out, long out_offset, int64_t* counts, void* stream);
+
+/* ---- VQ-KD visual tokenizer: nearest-code assignment (models/norm_ema_quantizer.py:149-162 NormEMAVectorQuantizer.forward; the MIM
+ * targets of models/xfm.py:624-629 through models/model_vqkd.py get_codebook_indices; ABI 20)
+ * xfm_vq_assign: z fp32 [M, K] (row r at z + r * z_ld), code fp32 [n_code, K] (row c at code + c * code_ld), in one launch
+ *   zn       = z[r] / max(||z[r]||_2, 1e-12)                                   (F.normalize, norm_ema_quantizer.py:153)
+ *   index[r] = argmin_c (|zn|^2 + |code[c]|^2 - 2 zn . code[c])                (norm_ema_quantizer.py:158-162)
+ * |code[c]|^2 is part of the score: the codebook is NOT assumed to be unit-norm.  |zn|^2, the same for every code of a row, is left out of
+ * the comparison.  EQUAL SCORES GO TO THE LOWEST CODE INDEX (torch.argmin's rule); every score is the same arithmetic wherever its code
+ * sits -- a k-ordered fp32 fmaf chain for the dot product (v_mfma_f32_32x32x2_f32: exact fp32 products and sums, no bf16), another for
+ * |code[c]|^2, one fmaf joining them -- so two equal codebook rows score bit-equal against every row and the lower index is returned.
+ * index int64 [M].  counts int32 [n_code], optional (NULL: not kept): counts[c] += the number of rows assigned to c -- the histogram
+ * that the eval-mode EMA of cluster_size consumes (norm_ema_quantizer.py:168-172); it ACCUMULATES across calls.  Integer atomics on global
+ * memory: an integer sum does not depend on the order.
+ * The [M, n_code] score matrix never exists in global memory and there is no workspace: one workgroup keeps 64 normalised rows in LDS,
+ * streams the codebook through LDS in chunks of 128 codes and carries a running (best, argbest) per row in registers.  Plain vector loads
+ * and stores, no floating-point atomics: the same bits on every launch, with and without XFM_DETERMINISTIC.
+ * A row with a non-finite component still gets an index in [0, n_code); which one is unspecified.  An all-zero row scores |code[c]|^2.
+ * XFM_E_ARG (nothing is launched): a NULL z / code / index; M < 1 or n_code < 1; z_ld < K or code_ld < K; z or code not 16-byte aligned,
+ * or a leading dimension not a multiple of 4.  XFM_E_UNSUPPORTED (nothing is launched): K not a multiple of 4 or outside [4, 64]. */
+int xfm_vq_assign(const float* z, long z_ld, int M, int K, const float* code, long code_ld, int n_code, int64_t* index, int* counts,
+                  void* stream);
 
 /* ---- Incremental decoding (models/xbert.py:1368-1484 prepare_inputs_for_generation / _generate_no_beam_search; the cached branches of the
  * attention at models/xroberta.py:224-262; ABI 17)

@@ -13,7 +13,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # XFM_HIP_LIB: A/B a differently built library (kernel experiments); the default is the in-tree build.
 LIB_PATH = os.environ.get("XFM_HIP_LIB") or os.path.join(_HERE, "libxfm_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 c_void_p, c_int, c_long, c_float, c_u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_uint32
 
@@ -220,6 +220,7 @@ SIGNATURES = {
     "xfm_xattn_gradcam": (c_int, [ctypes.POINTER(GradcamArgs), c_void_p]),
     "xfm_cam_box_rank": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p,
                                  c_long, c_void_p, c_void_p]),
+    "xfm_vq_assign": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p]),
     "xfm_decode_attn": (c_int, [ctypes.POINTER(DecodeAttnArgs), c_void_p]),
     "xfm_next_token": (c_int, [ctypes.POINTER(NextTokenArgs), c_void_p]),
     "xfm_sample_token": (c_int, [ctypes.POINTER(SampleTokenArgs), c_void_p]),

@@ -162,9 +162,10 @@ def arena_note_grad(mod):
 
 
 class ParamArena:
-    def __init__(self, module, slots=(), device=None):
+    def __init__(self, module, slots=(), device=None, exclude=()):
+        """exclude: submodules whose parameters stay OUT of the arena (a frozen tokenizer with an arena of its own)."""
         params = []
-        seen = set()
+        seen = {id(p) for m in exclude for p in m.parameters()}
         for name, p in module.named_parameters():
             if id(p) not in seen:
                 seen.add(id(p))

@@ -47,6 +47,7 @@ int xfm_cu_count() {
 #include "metrics.hip"
 #include "grounding.hip"
 #include "gradcam.hip"
+#include "vq.hip"
 #include "decode.hip"
 #include "dp.hip"
 
@@ -345,6 +346,10 @@ int xfm_xattn_gradcam(const xfm_gradcam_args* a, void* stream) {
 int xfm_cam_box_rank(const float* cam, int p, const int* img_hw, const double* det, const int* det_start, int max_dets, const double* ref_box,
                      const int* ref_split, int n, double alpha, double* out, long out_offset, int64_t* counts, void* stream) {
   return xfm_cam_box_rank_impl(cam, p, img_hw, det, det_start, max_dets, ref_box, ref_split, n, alpha, out, out_offset, counts, ST(stream));
+}
+int xfm_vq_assign(const float* z, long z_ld, int M, int K, const float* code, long code_ld, int n_code, int64_t* index, int* counts,
+                  void* stream) {
+  return xfm_vq_assign_impl(z, z_ld, M, K, code, code_ld, n_code, index, counts, ST(stream));
 }
 int xfm_box_eval(const float* coord, const int* ref_row, const float* ref_box, const float* ref_size, const int* ref_split, int n, int R,
                  float* out, long out_offset, int64_t* counts, void* stream) {

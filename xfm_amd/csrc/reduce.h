@@ -24,6 +24,15 @@ __device__ __forceinline__ int wave_sum_int(int v) {
   return v;
 }
 
+// One step of an argmin that keeps the LOWEST index among equal values (torch.argmin's rule): (ov, oi) replaces (v, i) when it is smaller
+// in (value, index) order.  A NaN on either side replaces nothing.
+__device__ __forceinline__ void argmin_merge(float& v, int& i, float ov, int oi) {
+  if (ov < v || (ov == v && oi < i)) {
+    v = ov;
+    i = oi;
+  }
+}
+
 // Reductions over a 256-lane workgroup (four waves) through red, four floats of LDS that the caller supplies; every lane gets the
 // result.  The first barrier waits for earlier readers of red, so calls may follow one another on the same four slots.
 __device__ __forceinline__ void block_park256(float wave_value, float* red) {

@@ -1074,6 +1074,30 @@ def cam_box_rank(cam, img_hw, det, det_start, max_dets, ref_box, ref_split, alph
     return out
 
 
+def vq_assign(z, code, counts=None, out=None):
+    """xfm_vq_assign: z fp32 [M, K] and code fp32 [n_code, K], 2-D with unit column stride (row-strided slices will do, rows on 16 bytes).
+    Returns index int64 [M] = argmin_c |code[c]|^2 - 2 normalize(z[r]) . code[c], equal scores to the lowest index
+    (norm_ema_quantizer.py:153-162).  counts int32 [n_code] (optional) += the histogram of the indices.  out: a contiguous int64 [M] to
+    write the indices to.  K must be a multiple of 4 in [4, 64] (XFM_E_UNSUPPORTED otherwise)."""
+    for t in (z, code):
+        _dev(t)
+        assert t.dtype == F32 and t.dim() == 2 and t.stride(1) == 1
+    M, K = z.shape
+    n_code = code.shape[0]
+    assert code.shape[1] == K
+    if counts is not None:
+        _dev(counts)
+        assert counts.dtype == torch.int32 and counts.numel() == n_code and counts.is_contiguous()
+    if out is None:
+        out = torch.empty(M, dtype=torch.int64, device=z.device)
+    else:
+        _dev(out)
+        assert out.dtype == torch.int64 and out.numel() == M and out.is_contiguous()
+    check(_lib.load().xfm_vq_assign(z.data_ptr(), z.stride(0), M, K, code.data_ptr(), code.stride(0), n_code, out.data_ptr(), _ptr(counts),
+                                    _stream()), "vq_assign")
+    return out
+
+
 def decode_attn(q, k_cache, v_cache, cap, H, scale, k_new=None, v_new=None, pos=0, Sk=None, key_keep=None, kv_index=None, out=None):
     """xfm_decode_attn: one new query token per batch row against a token-major key/value cache (xroberta.py:224-262 with a past).
     q [B, >= H*64] bf16 (a column slice of the QKV GEMM output will do); k_cache / v_cache: 2-D bf16 views [entries * cap, >= H*64] of the

@@ -223,16 +223,17 @@ class XFM(XFMBase):
             if image_embeds_masked is None:
                 image_embeds_masked, _, ids_mask = self.get_vision_embeds(image, do_mask=self.do_image_mask, ids_mask=ids_mask)
             if do_mim:
+                mim_target = image if self.use_vision_tokenizer else image_embeds   # model_pretrain.py:70-75
                 ms = mim_stream
                 if ms is not None:   # the masked view lives on its own stream: its loss too; the main stream joins once, here
                     cur = torch.cuda.current_stream(image.device)
                     ms.wait_stream(cur)   # (the clean view's embeddings are the target)
                     with torch.cuda.stream(ms):
-                        loss_mim = self.get_mim_loss(image_embeds_masked, image_embeds, ids_mask)
+                        loss_mim = self.get_mim_loss(image_embeds_masked, mim_target, ids_mask)
                     cur.wait_stream(ms)
                     loss_mim.record_stream(cur)
                 else:
-                    loss_mim = self.get_mim_loss(image_embeds_masked, image_embeds, ids_mask)
+                    loss_mim = self.get_mim_loss(image_embeds_masked, mim_target, ids_mask)
             if w is not None:
                 loss_mim = loss_mim * w
         loss_bbox = loss_giou = zero

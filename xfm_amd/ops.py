@@ -277,6 +277,52 @@ def lm_head_ce(x, head, labels, reduction="mean", label_smoothing=0.0):
     return _LMHeadCEFn.apply(x.contiguous(), head, labels, reduction, float(label_smoothing))
 
 
+class _LinearCEFn(torch.autograd.Function):
+    """Mean cross-entropy (ignore_index -100) of one Linear's logits: the token head of the VQ-KD MIM branch, xfm.py:629
+    (`loss_ce(lm_head(x), input_ids)`).  The fp32 logits and their bf16 gradient stay inside the node; rows labelled -100 cost the GEMMs
+    their share but contribute nothing to the loss or to any gradient."""
+
+    @staticmethod
+    def forward(ctx, x, slot, labels, anchor):
+        x2 = x.reshape(-1, x.shape[-1])
+        x2 = (x2 if x2.dtype == BF16 else x2.to(BF16)).contiguous()
+        V = slot.N
+        ldl = (V + VOCAB_LD - 1) // VOCAB_LD * VOCAB_LD
+        logits = torch.empty((x2.shape[0], ldl), dtype=F32, device=x2.device)
+        Fx.gemm_nt(x2, slot.wb, slot.b, epi=Fx.EPI_F32, out=logits, n=V)
+        labels = labels.reshape(-1).contiguous()
+        lse, loss_rows = Fx.ce_fwd(logits, V, labels)
+        nvalid = (labels != -100).sum().clamp(min=1).to(F32)
+        ctx.saved = (x2, logits, labels, lse, nvalid)
+        ctx.slot, ctx.xshape, ctx.xdtype = slot, x.shape, x.dtype
+        return loss_rows.sum() / nvalid
+
+    @staticmethod
+    def backward(ctx, g):
+        x2, logits, labels, lse, nvalid = ctx.saved
+        s = ctx.slot
+        V, ldl = s.N, logits.shape[1]
+        dlogits = Fx.ce_bwd(logits, V, labels, lse, (g / nvalid).reshape(1).to(F32).contiguous(), ldl)
+        wg = _WgradStream(x2.device)
+        wg.gemm_tn(dlogits, x2, s.dw, n=V, dbias=s.db)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            if ldl <= s.wt.shape[1]:
+                dx = Fx.gemm_nt(dlogits, s.wt[:, :ldl], n=s.K)
+            else:   # a head narrower than the 64-column granularity of the contraction: zero-pad the transposed weight to it
+                wtp = torch.zeros((s.K, ldl), dtype=BF16, device=x2.device)
+                wtp[:, :V] = s.wt[:, :V]
+                dx = Fx.gemm_nt(dlogits, wtp, n=s.K)
+            dx = dx.view(ctx.xshape).to(ctx.xdtype)
+        wg.join_at_end()
+        return dx, None, None, None
+
+
+def linear_ce(x, slot, labels):
+    """mean_{labels != -100} CE(x @ W^T + b, labels) through the bf16 MFMA GEMM and the vocabulary cross-entropy kernels."""
+    return _LinearCEFn.apply(x, slot, labels, slot.weights[0])
+
+
 def lm_head_logits(x, head):
     """Inference-only logits (return_logits=True path, xroberta.py:1287-1288)."""
     sd, sv = head._slot_dense, head._slot_decoder

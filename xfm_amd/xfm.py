@@ -25,7 +25,7 @@ from . import marks as _marks
 from .arena import LinearSlot, ParamArena
 from . import beit2 as _beit2
 from .beit2 import _Affine, beit_base_patch16
-from .ops import itc_loss, layer_norm, linear_slot, row_normalize, small_ce
+from .ops import itc_loss, layer_norm, linear_ce, linear_slot, row_normalize, small_ce
 from .roberta_layer import _next_seed
 from .xroberta import RobertaConfig, RobertaForMaskedLM, _Lin, rowwise
 
@@ -129,6 +129,16 @@ def _read_json(path, default):
         with open(path) as f:
             return json.load(f)
     return dict(default)
+
+
+def get_visual_tokenizer(tokenizer_model, tokenizer_weight, image_res, codebook_size, codebook_dim, encoder_depth=12):
+    """xfm.py:104-112: the frozen VQ-KD tokenizer, in eval mode.  `tokenizer_weight` None (extension): fresh weights, for a later
+    load_state_dict; `encoder_depth` (extension, config key `tokenizer_depth`): a shallower encoder for tests."""
+    if tokenizer_model != 'vqkd_encoder_base_decoder_3x768x12_clip':
+        raise ValueError(tokenizer_model)
+    from .model_vqkd import vqkd_encoder_base_decoder_3x768x12_clip
+    return vqkd_encoder_base_decoder_3x768x12_clip(pretrained=True, pretrained_weight=tokenizer_weight, as_tokenzer=True, img_size=image_res,
+                                                   n_code=codebook_size, code_dim=codebook_dim, encoder_depth=encoder_depth).eval()
 
 
 def build_vision_encoder(config, load_params=False):
@@ -288,8 +298,10 @@ class XFMBase(nn.Module):
         self.vision_width = vision_width
         self.text_width = self.text_encoder.config.hidden_size
         self.use_vision_tokenizer = config.get('use_vision_tokenizer', False)
-        if self.use_vision_tokenizer:
-            raise NotImplementedError("VQ-KD visual tokenizer (model_vqkd.py) is outside the hot-path scope")
+        if self.use_vision_tokenizer:   # xfm.py:488-496: MIM targets are the tokens of a frozen VQ-KD tokenizer
+            self.vqkd = get_visual_tokenizer(config['tokenizer_model'], config.get('tokenizer_weight'), config['image_res'],
+                                             config['codebook_size'], config['codebook_dim'], encoder_depth=config.get('tokenizer_depth', 12))
+            self.lm_head = _Lin(self.vision_width, config['codebook_size'], 0.02)
         if use_contrastive_loss:
             self.embed_dim = config['embed_dim']
             self.vision_proj = _Lin(self.vision_width, self.embed_dim, 0.02)
@@ -356,7 +368,12 @@ class XFMBase(nn.Module):
             slots += self.cls_head.linear_slots("cls_head.")
         if hasattr(self, "text_decoder"):  # the answer decoder of model_generation.py
             slots += self.text_decoder.linear_slots("text_decoder.")
-        self._arena = ParamArena(self, slots, device)
+        exclude = ()
+        if hasattr(self, "vqkd"):   # the frozen tokenizer keeps an arena of its own: nothing of it is exchanged, clipped or stepped
+            self._s_lm_head = LinearSlot("lm_head", [self.lm_head.weight], [self.lm_head.bias])
+            slots.append(self._s_lm_head)
+            exclude = (self.vqkd,)
+        self._arena = ParamArena(self, slots, device, exclude=exclude)
         self.vision_encoder.attach(self._arena)
         self.text_encoder.attach(self._arena)
         self.fusion_encoder.attach(self._arena)
@@ -687,5 +704,14 @@ class XFMBase(nn.Module):
                                    masked_pos=masked_pos).loss
 
     def get_mim_loss(self, image_embeds_masked, targets, mask_tokens):
-        """MSE(masked patches) + MSE(pooled cls), xfm.py:624-635: one fused pass each way, sync-free masked mean."""
+        """MSE(masked patches) + MSE(pooled cls), xfm.py:624-635: one fused pass each way, sync-free masked mean.
+        With `use_vision_tokenizer` (xfm.py:625-629) `targets` are the raw images: their VQ-KD tokens under no_grad, then the mean
+        cross-entropy of lm_head over the masked patch rows.  The head runs over EVERY patch row with the unmasked ones labelled -100
+        (no boolean indexing: no host read; profiles/vq_tokenizer.md has the cost against a compacted row set)."""
+        if self.use_vision_tokenizer:
+            self._ready()
+            with torch.no_grad():
+                input_ids = self.vqkd.get_codebook_indices(targets)
+            labels = torch.where(mask_tokens.to(device=input_ids.device, dtype=torch.bool), input_ids, -100)
+            return linear_ce(image_embeds_masked[:, 1:, :], self._s_lm_head, labels)
         return _MimLossFn.apply(image_embeds_masked, targets.detach(), mask_tokens, not self.mim_cls_only)
