@@ -197,7 +197,7 @@ class RCCLDDPAccelerator(Accelerator):
         tower's share a queue, and the text backward starts 11 ms late behind a collective that waits for a hand-over event).  Here
         every stream of the step is created and used once, in an order chosen for the sharing it produces; `nccl` stands for the
         set-up broadcast (ProcessGroupNCCL's first collective = its stream's first use)."""
-        from ..model_pretrain import _side_stream
+        from ..model_pretrain import _SIDE_STREAMS, _stream_of
         dev = torch.device("cuda", local_rank)
         main = torch.cuda.current_stream(dev)
 
@@ -207,11 +207,11 @@ class RCCLDDPAccelerator(Accelerator):
                     self.broadcast()
                 continue
             if name == "text":
-                st = _side_stream(dev)
+                st = _stream_of(_SIDE_STREAMS, dev)
             elif name == "wmain":
                 st = _WgradStream.side_of(dev, main)
             elif name == "wtext":
-                st = _WgradStream.side_of(dev, _side_stream(dev))
+                st = _WgradStream.side_of(dev, _stream_of(_SIDE_STREAMS, dev))
             elif name == "cast":
                 if self.arena._cast_stream is None:
                     self.arena._cast_stream = torch.cuda.Stream(device=dev)
@@ -275,7 +275,7 @@ class RCCLDDPAccelerator(Accelerator):
         for name, mod, rng in self._towers:
             if not hasattr(mod, "roberta"):
                 # the vision tower finishes last and its patch-embed / cls gradients trail the trunk (swept after backward), but
-                # the trunk's blocks can leave in chunks from inside its backward (beit2._TrunkFn.backward)
+                # the trunk's blocks can leave in chunks from inside its backward (vit_trunk._TrunkFn.backward)
                 if hasattr(mod, "blocks"):
                     self._use[id(mod)] = [0, name, None]
                     mod._use_hook = self._on_use

@@ -14,9 +14,11 @@ import torch
 import torch.nn as nn
 
 from . import functional as Fx
-from .arena import LinearSlot, OwnsArena, ParamArena, arena_note_grad, arena_note_use, grad_of
-from .ops import linear_slot
-from .side_stream import _WgradStream
+from .arena import grad_of
+# the containers, the trunk node and its knobs live in vit_trunk.py and stay importable from here; the knob names are read-only copies
+# (the live values are vit_trunk's: assigning to one here changes nothing)
+from .vit_trunk import (_DEFER_LN, _DEFER_WGRAD, _FAST_DELTA, _GRAD_CHUNK_BLOCKS, _RELPOS_AHEAD, _VIT_FUSED_BWD,  # noqa: F401
+                        _WGRAD_GROUP_BLOCKS, PatchEmbed, _Affine, _Dense, _FusedViT, _TrunkFn)
 
 
 class BlockMaskGenerator:
@@ -90,26 +92,6 @@ def build_relative_position_index(gh, gw):
     return idx
 
 
-class _Affine(nn.Module):
-    """weight/bias container for a LayerNorm (arithmetic runs in the fused HIP kernels)."""
-
-    def __init__(self, dim, eps):
-        super().__init__()
-        self.weight = nn.Parameter(torch.ones(dim))
-        self.bias = nn.Parameter(torch.zeros(dim))
-        self.eps = eps
-
-
-class _Dense(nn.Module):
-    """weight/bias container for a Linear."""
-
-    def __init__(self, fin, fout, bias=True):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(fout, fin))
-        self.bias = nn.Parameter(torch.zeros(fout)) if bias else None
-        nn.init.trunc_normal_(self.weight, std=0.02, a=-2.0, b=2.0)
-
-
 class Attention(nn.Module):
     def __init__(self, dim, num_heads, window_size):
         super().__init__()
@@ -142,198 +124,6 @@ class Block(nn.Module):
         self.gamma_1 = nn.Parameter(init_values * torch.ones(dim))
         self.gamma_2 = nn.Parameter(init_values * torch.ones(dim))
         self.drop_path_prob = float(drop_path)
-
-
-class PatchEmbed(nn.Module):
-    def __init__(self, img_size, patch_size, in_chans, embed_dim):
-        super().__init__()
-        self.img_size = (img_size, img_size)
-        self.patch_size = (patch_size, patch_size)
-        self.patch_shape = (img_size // patch_size, img_size // patch_size)
-        self.num_patches = self.patch_shape[0] * self.patch_shape[1]
-        self.proj = nn.Module()
-        self.proj.weight = nn.Parameter(torch.empty(embed_dim, in_chans, patch_size, patch_size))
-        self.proj.bias = nn.Parameter(torch.zeros(embed_dim))
-        nn.init.kaiming_uniform_(self.proj.weight, a=math.sqrt(5))
-
-
-def _block_bias(vit, blk, H, N, ld, need_grad):
-    """(dense, dense_t, tiles) of one block's relative-position bias, as _TrunkFn.forward builds them."""
-    long_n = N > 256 and need_grad   # (long sequences: the dK/dV kernel reads the tiled transposed copy, no dense one)
-    dense = Fx.relpos_gather(blk.attn.relative_position_bias_table, vit._index32, H, N, ld, transposed=not long_n)
-    dense_t = tiles = None
-    if not long_n:
-        dense, dense_t = dense
-    if 64 < N <= 224:   # the batch-walking ViT-shape kernels (csrc/attention_vit.hip) read accumulator-layout copies
-        tiles = Fx.bias_tiles(dense, N, blk.attn.scale, fwd=True, bwd=_VIT_FUSED_BWD and need_grad)
-    elif N > 256 and need_grad:   # 384 / 480 px: the long-sequence backward kernels (csrc/attention_long.hip) read both copies
-        tiles = Fx.bias_tiles(dense, N, blk.attn.scale, fwd=True, bwd=True)
-    return dense, dense_t, tiles
-
-
-class _TrunkFn(torch.autograd.Function):
-    """All transformer blocks + the final LayerNorm as one node.  x0: fp32 [B, N, D] -> bf16 [B, N, D]."""
-
-    @staticmethod
-    def forward(ctx, x0, vit, dp):
-        B, N, D = x0.shape
-        M, H = B * N, vit.num_heads
-        arena = vit._arena
-        x = x0.reshape(M, D).contiguous()
-        ld = vit._bias_ld
-        blocks = vit.blocks
-        saved = []
-        n0 = blocks[0].norm1
-        y, mean, rstd = Fx.ln_fwd(x, n0.weight, n0.bias, n0.eps)
-        ctx.first = (x, mean, rstd)
-        rel_pos = getattr(vit, "_rel_pos", True)      # models/vit.py (plain ViT): no relative-position bias,
-        final_norm = vit._final_norm if hasattr(vit, "_final_norm") else vit.fc_norm
-        # the blocks' dense relative-position biases (table gather + accumulator-layout copies: two 5-us kernels per block) depend on the
-        # weights alone: all 24 launches go to the second stream up front and run under the first block's GEMMs
-        ahead = None
-        if rel_pos and x.is_cuda and _RELPOS_AHEAD:
-            pre = _WgradStream(x.device)
-            if pre.on:
-                ahead = []
-                with torch.cuda.stream(pre.side):
-                    for blk in blocks:
-                        ahead.append(_block_bias(vit, blk, H, N, ld, bool(ctx.needs_input_grad[0])))
-                    ev_bias = torch.cuda.Event()
-                    ev_bias.record(pre.side)
-                for triple in ahead:
-                    for t in triple[:2] + tuple(triple[2] or ()):
-                        if t is not None:
-                            t.record_stream(pre.main)
-                pre.main.wait_event(ev_bias)
-        for i, blk in enumerate(blocks):
-            s = vit._slots[i]
-            g1 = blk.gamma_1 if blk.gamma_1 is not None else vit._ones   # ... and no layer scale (gamma = 1, no gradient)
-            g2 = blk.gamma_2 if blk.gamma_2 is not None else vit._ones
-            dense = dense_t = tiles = None
-            if ahead is not None:
-                dense, dense_t, tiles = ahead[i]
-            elif rel_pos:
-                dense, dense_t, tiles = _block_bias(vit, blk, H, N, ld, bool(ctx.needs_input_grad[0]))
-            qkv = Fx.gemm_nt(y, s["qkv"].wb, s["qkv"].b)
-            # long sequences keep the low half of O: the backward then takes delta from dO . (O + O_lo) instead of a first pass over
-            # the keys (two of the dQ kernel's five matrix products: 355 -> 224 us per layer at 901 tokens for 24 us of forward)
-            if ctx.needs_input_grad[0] and (_FAST_DELTA or N > 256):
-                ctxv, lse, ctxv_lo = Fx.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, H, N, N, blk.attn.scale, bias=dense, lo=True,
-                                                 bias_tiles=tiles)
-            else:
-                (ctxv, lse), ctxv_lo = Fx.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, H, N, N, blk.attn.scale, bias=dense,
-                                                   bias_tiles=tiles), None
-            h1 = Fx.gemm_nt(ctxv, s["proj"].wb, s["proj"].b)
-            dp1 = None if dp is None else dp[i, 0]
-            dp2 = None if dp is None else dp[i, 1]
-            x1, y2, mean2, rstd2 = Fx.ln_ls_fwd(x, h1, g1, dp1, N, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
-            hact, u = Fx.gemm_nt(y2, s["fc1"].wb, s["fc1"].b, epi=Fx.EPI_GELU)
-            h2 = Fx.gemm_nt(hact, s["fc2"].wb, s["fc2"].b)
-            nxt = blocks[i + 1].norm1 if i + 1 < len(blocks) else final_norm
-            x2, yn, meann, rstdn = Fx.ln_ls_fwd(x1, h2, g2, dp2, N, nxt.weight, nxt.bias, nxt.eps)
-            saved.append((y, dense, qkv, ctxv, lse, h1, x1, mean2, rstd2, y2, u, hact, h2, x2, meann, rstdn, dp1, dp2, dense_t, ctxv_lo, tiles))
-            x, y = x2, yn
-        ctx.saved, ctx.vit, ctx.shape = saved, vit, (B, N, D)
-        ctx.noted = bool(ctx.needs_input_grad[0])
-        if ctx.noted:
-            arena_note_use(vit)
-        ctx.pooled = bool(getattr(vit, "_pool_tail", False))
-        if ctx.pooled:  # beit2.py:455-466: the cls row leaves as the mean of the normalised patch rows (in place: y is not saved)
-            Fx.pool_rows_fwd_(y, B, N)
-        return y.view(B, N, D)
-
-    @staticmethod
-    def backward(ctx, dy_out):
-        vit, (B, N, D) = ctx.vit, ctx.shape
-        M, H = B * N, vit.num_heads
-        blocks = vit.blocks
-        ld = vit._bias_ld
-        # two passes of one step (clean / MIM-masked view) may run on different streams; their weight gradients accumulate (+=) into the
-        # same arena ranges, so a pass starts only once the previous one -- wherever it ran -- has finished
-        prev = getattr(vit, "_trunk_bwd_done", None)
-        if prev is not None and dy_out.is_cuda:
-            torch.cuda.current_stream(dy_out.device).wait_event(prev)
-        dy = dy_out.reshape(M, D).contiguous()
-        if ctx.pooled:
-            dy = Fx.pool_rows_bwd(dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16), B, N)
-        dstream = torch.zeros((M, D), dtype=torch.float32, device=dy.device)
-        wg = _WgradStream(dy.device, "vit bwd")
-        done = len(blocks)
-        ddense_all = None
-        # the blocks' weight gradients are QUEUED and run as one grouped launch at the end of the trunk (or before each hand-over of a
-        # gradient range to the data-parallel accelerator below): 48 projections x 9-36 output tiles walk whole tiles over all of M
-        queued = _DEFER_WGRAD and dy.is_cuda
-        tn = wg.defer_tn if queued else wg.gemm_tn
-        # ... and so are the column-sum folds of the two LayerNorm backward kernels of a block (dgamma / dbeta / bias / layer-scale gradients)
-        rq = None
-        if _DEFER_LN and dy.is_cuda:
-            from . import _lib
-            rq = Fx.ReduceQueue(dy.device, 2 * len(blocks) * ((_lib.load().xfm_layernorm_bwd_workspace(M, D, 2) + 255) // 256 * 256))   # LN_LS
-            wg.defer_reduces(rq)
-        for i in reversed(range(len(blocks))):
-            blk, s = blocks[i], vit._slots[i]
-            (y, dense, qkv, ctxv, lse, h1, x1, mean2, rstd2, y2, u, hact, h2, x2, meann, rstdn, dp1, dp2, dense_t, ctxv_lo, tiles) = ctx.saved[i]
-            final_norm = vit._final_norm if hasattr(vit, "_final_norm") else vit.fc_norm
-            nxt = blocks[i + 1].norm1 if i + 1 < len(blocks) else final_norm
-            g = grad_of
-            g1 = blk.gamma_1 if blk.gamma_1 is not None else vit._ones
-            g2 = blk.gamma_2 if blk.gamma_2 is not None else vit._ones
-            dg1 = g(blk.gamma_1) if blk.gamma_1 is not None else None
-            dg2 = g(blk.gamma_2) if blk.gamma_2 is not None else None
-            dh2 = Fx.ln_ls_bwd(dy, dstream, x2, meann, rstdn, nxt.weight, h2, g2, dp2, N, g(nxt.weight), g(nxt.bias),
-                               s["fc2"].db, dg2, defer=rq)
-            tn(dh2, hact, s["fc2"].dw)
-            du = Fx.gemm_nt(dh2, s["fc2"].wt, epi=Fx.EPI_DGELU, aux=u, n=s["fc2"].K)
-            tn(du, y2, s["fc1"].dw, dbias=s["fc1"].db)
-            dy2 = Fx.gemm_nt(du, s["fc1"].wt, n=s["fc1"].K)
-            dh1 = Fx.ln_ls_bwd(dy2, dstream, x1, mean2, rstd2, blk.norm2.weight, h1, g1, dp1, N, g(blk.norm2.weight),
-                               g(blk.norm2.bias), s["proj"].db, dg1, defer=rq)
-            tn(dh1, ctxv, s["proj"].dw)
-            dctx = Fx.gemm_nt(dh1, s["proj"].wt, n=s["proj"].K)
-            dqkv = torch.empty_like(qkv)
-            ddense = None
-            if dense is not None:  # one zero fill for the whole trunk's bias-gradient scratch instead of one per block
-                if ddense_all is None:
-                    ddense_all = torch.zeros((len(blocks),) + tuple(dense.shape), dtype=dense.dtype, device=dense.device)
-                ddense = ddense_all[i]
-            Fx.attn_bwd(dctx, qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ctxv, lse, dqkv[:, :D], dqkv[:, D:2 * D],
-                        dqkv[:, 2 * D:], B, H, N, N, blk.attn.scale, bias=dense, dbias=ddense, bias_t=dense_t, o_lo=ctxv_lo,
-                        bias_tiles=tiles if (_VIT_FUSED_BWD or N > 256) else None)
-            if dense is not None:   # the TABLE gradient from the dense bias gradient: a parameter gradient -- runs with the queued weight gradients
-                G = blk.attn.window_size[0]
-                dtab = g(blk.attn.relative_position_bias_table)
-                if N > 256 and blk.attn.window_size[0] == blk.attn.window_size[1] and N == G * G + 1:
-                    fn = lambda ddense=ddense, G=G, dtab=dtab: Fx.relpos_grid_grad(ddense, G, H, ld, dtab)   # noqa: E731  (144 -> ~20 us at 901 tokens)
-                else:
-                    fn = lambda ddense=ddense, dtab=dtab: Fx.relpos_scatter_sorted(ddense, vit._relpos_order, vit._relpos_start, H, N, ld, dtab)   # noqa: E731
-                if queued:
-                    wg.defer_call(fn, keep=(ddense_all,))
-                else:
-                    fn()
-            tn(dqkv, y, s["qkv"].dw, dbias=s["qkv"].db)
-            dy = Fx.gemm_nt(dqkv, s["qkv"].wt, n=s["qkv"].K)
-            ctx.saved[i] = None
-            if _WGRAD_GROUP_BLOCKS > 0 and i % _WGRAD_GROUP_BLOCKS == 0:
-                wg.flush()
-            # data parallel: the gradients of blocks [i + 1, done) are final now (block i's own norm1 gradient is only written while
-            # block i - 1 is processed) once this pass is the tower's last pending use -- hand that arena range to the accelerator,
-            # so its all-reduce runs under the remaining blocks' backward
-            if ctx.noted and i > 0 and i % _GRAD_CHUNK_BLOCKS == 0 and i + 1 < done:
-                hook = getattr(vit, "_block_grad_hook", None)
-                # (the hook flushes the queued weight gradients itself once it knows the range really leaves now)
-                if hook is not None and hook(vit, i + 1, done, wg):
-                    done = i + 1
-        x0, mean0, rstd0 = ctx.first
-        n0 = blocks[0].norm1
-        Fx.ln_bwd(dy, x0, mean0, rstd0, n0.weight, grad_of(n0.weight), grad_of(n0.bias), dx32=dstream, dx_accum=True)
-        wg.join()
-        if dstream.is_cuda:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dstream.device))
-            vit._trunk_bwd_done = ev
-        if ctx.noted:
-            arena_note_grad(vit)
-        return dstream.view(B, N, D), None, None
 
 
 class _RegionPoolFn(torch.autograd.Function):
@@ -390,28 +180,11 @@ class _TokensFn(torch.autograd.Function):
         return dtok, None, None, None, None
 
 
-# XFM_ATTN_FAST_DELTA=1: the attention backward takes delta = dO . O from the forward's output (kept as bf16 hi + lo halves) instead of a
-# first pass over the keys: dQ kernel 198 -> 165 us, forward 69 -> 80 us at B = 128 (tools/bench_attn.py), the step unchanged within
-# noise (41.6 vs 41.5 ms, tools/ab.sh) -- off by default, the exact two-pass form costs nothing
-_FAST_DELTA = os.environ.get("XFM_ATTN_FAST_DELTA", "0") != "0"
-_VIT_FUSED_BWD = os.environ.get("XFM_ATTN_VIT_BWD", "0") != "0"   # opt-in single-pass attention backward (measured slower than the split pair: csrc/attention_vit.hip)
-# the trunk's gradients leave for the all-reduce in chunks of this many blocks, from inside its backward; what is still there when the
-# backward ends (blocks 0 .. chunk, the embeddings) is the exposed tail of the exchange: 2 -> 3 blocks = 85 MB of fp32 gradients behind
-# five overlapped 57-MB collectives (round 2: 4 -> 5 blocks = 142 MB behind two of 114 MB)
-# XFM_VIT_DEFER_WGRAD=0: one xfm_gemm_tn per projection as the backward reaches it (rounds 1-3) instead of the grouped launch
-_DEFER_WGRAD = os.environ.get("XFM_VIT_DEFER_WGRAD", "1") != "0"
-_RELPOS_AHEAD = os.environ.get("XFM_VIT_RELPOS_AHEAD", "1") != "0"   # A/B knob: the blocks' dense biases built up front on the second stream
-_DEFER_LN = os.environ.get("XFM_VIT_DEFER_LN", "1") != "0"   # A/B knob: one batched LayerNorm column-sum reduce for the trunk
-_WGRAD_GROUP_BLOCKS = int(os.environ.get("XFM_VIT_WGRAD_GROUP", "0"))   # blocks per grouped launch (0: the whole trunk at its end)
-# (round 4: every hand-over also launches the chunk's queued weight gradients as one grouped call -- 0.43 ms per block in chunks of two,
-# 0.37 in chunks of four, 0.33 for the whole trunk at once -- so chunks of four again: 0.6 ms less weight-gradient time than chunks of
-# two for ~0.25 ms more exposed exchange (blocks 0-4 instead of 0-2 after the backward))
-_GRAD_CHUNK_BLOCKS = max(1, int(os.environ.get("XFM_VIT_GRAD_CHUNK", "4")))
-
-
-class VisionTransformer(OwnsArena, nn.Module):
+class VisionTransformer(_FusedViT):
     """Drop-in for models.beit2.VisionTransformer (BEiT-v2 configuration used by XFM)."""
+    _rel_pos = True
     _pool_tail = True  # forward_avgpool (beit2.py:455-466): the trunk node replaces the cls row by the mean of the patch rows
+    _draw_at_rate_zero = True  # drop-path scales are drawn on every training forward: the device RNG advances even when no block drops
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12, num_heads=12,
                  mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
@@ -449,47 +222,19 @@ class VisionTransformer(OwnsArena, nn.Module):
         for i, blk in enumerate(self.blocks):  # fix_init_weight, beit2.py:327-333
             blk.attn.proj.weight.data.div_(math.sqrt(2.0 * (i + 1)))
             blk.mlp.fc2.weight.data.div_(math.sqrt(2.0 * (i + 1)))
-        self._arena = None
-        self._own_arena = False
 
-    # ---- arena plumbing -----------------------------------------------------------------------
-    def linear_slots(self):
-        D = self.embed_dim
-        self._slots = []
-        out = []
-        self._slot_patch = LinearSlot("patch_embed", [self.patch_embed.proj.weight], [self.patch_embed.proj.bias])
-        self._slot_patch.need_t = False
-        out.append(self._slot_patch)
-        for i, blk in enumerate(self.blocks):
-            s = {"qkv": LinearSlot(f"blocks.{i}.qkv", [blk.attn.qkv.weight], [blk.attn.q_bias, D, blk.attn.v_bias]),
-                 "proj": LinearSlot(f"blocks.{i}.proj", [blk.attn.proj.weight], [blk.attn.proj.bias]),
-                 "fc1": LinearSlot(f"blocks.{i}.fc1", [blk.mlp.fc1.weight], [blk.mlp.fc1.bias]),
-                 "fc2": LinearSlot(f"blocks.{i}.fc2", [blk.mlp.fc2.weight], [blk.mlp.fc2.bias])}
-            self._slots.append(s)
-            out.extend(s.values())
-        return out
+    @property
+    def _final_norm(self):
+        return self.fc_norm
+
+    def _qkv_bias_parts(self, blk):
+        return [blk.attn.q_bias, self.embed_dim, blk.attn.v_bias]   # no k bias: D structural zeros between the two
 
     def attach(self, arena):
-        self._arena = arena
-        N = self.patch_embed.num_patches + 1
-        self._bias_ld = (N + 15) // 16 * 16
+        super().attach(arena)
         self._index32 = self.blocks[0].attn.relative_position_index.to(device=arena.device, dtype=torch.int32).contiguous()
         self._relpos_order, self._relpos_start = Fx.relpos_sorted_index(
             self._index32, self.blocks[0].attn.relative_position_bias_table.shape[0])
-
-    def finalize(self, device=None):
-        """Stand-alone use (the XFM wrapper builds one arena for all towers instead)."""
-        device = device or self.cls_token.device
-        arena = ParamArena(self, self.linear_slots(), device)
-        self.attach(arena)
-        self._own_arena = True
-        return self
-
-    def _ready(self):
-        if self._arena is None or not self._arena.attached():
-            if self._arena is not None and not self._own_arena:
-                raise RuntimeError("parameters were moved after the arena was built; call finalize() again")
-            self.finalize()
 
     # ---- forward --------------------------------------------------------------------------------
     def forward(self, x, idx_to_group_img=None, image_atts=None, do_mask=False, ids_mask=None, drop_path_scales=None, split_stream=None):
@@ -503,10 +248,7 @@ class VisionTransformer(OwnsArena, nn.Module):
             raise ValueError("the region call form has no masked view (beit2.py:467-475)")
         self._ready()
         B = x.shape[0]
-        D = self.embed_dim
-        P = self.patch_embed.patch_size[0]
-        patches = Fx.patchify(x.float().contiguous(), P)
-        tok = linear_slot(patches, self._slot_patch, x_requires_grad=False, out_fp32=True).view(B, -1, D)
+        tok = self._patch_tokens(x)
         mask_u8 = None
         if do_mask:
             if ids_mask is None:
@@ -519,13 +261,7 @@ class VisionTransformer(OwnsArena, nn.Module):
             B = ids_mask.shape[0]
         # mask-token mix + cls concat (beit2.py:432-446) as one kernel, forward and backward
         x0 = _TokensFn.apply(tok, self.cls_token, self.mask_token, mask_u8, B)
-        dp = drop_path_scales
-        if dp is None and self.training:
-            keep = getattr(self, "_dp_keep", None)
-            if keep is None or keep.device != x.device:  # built once: a per-forward torch.tensor(..., device=cuda) would sync
-                keep = 1.0 - torch.tensor([[b.drop_path_prob] * 2 for b in self.blocks], device=x.device).view(-1, 2, 1)
-                self._dp_keep = keep
-            dp = (torch.rand(len(self.blocks), 2, B, device=x.device) < keep).float() / keep
+        dp = drop_path_scales if drop_path_scales is not None else self._drop_path_scales(B, x.device)
         if split_stream is not None and do_mask and B == 2 * x.shape[0]:
             Bh = x.shape[0]
             main = torch.cuda.current_stream(x.device)

@@ -3,6 +3,7 @@ import os
 
 import torch
 
+from . import marks as _marks
 from .xfm import XFMBase
 
 _TEXT_STREAM_ON = os.environ.get("XFM_TEXT_STREAM", "1") != "0"
@@ -15,22 +16,12 @@ _SIDE_STREAMS = {}
 _MIM_STREAMS = {}
 
 
-def _mim_stream(device):
+def _stream_of(streams, device):
+    """The device's stream in `streams` (_SIDE_STREAMS: the text tower; _MIM_STREAMS: the MIM-masked view), created on first use."""
     key = device.index if device.index is not None else torch.cuda.current_device()
-    if key not in _MIM_STREAMS:
-        _MIM_STREAMS[key] = torch.cuda.Stream(device=device)
-    return _MIM_STREAMS[key]
-
-
-def _side_stream(device):
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
-    return _SIDE_STREAMS[key]
-
-
-
-from . import marks as _marks  # noqa: E402
+    if key not in streams:
+        streams[key] = torch.cuda.Stream(device=device)
+    return streams[key]
 
 
 class _JoinAfterBackward(torch.autograd.Function):
@@ -73,7 +64,7 @@ def towers_side_by_side(model, image, text_ids, text_atts):
         image_embeds, image_atts = model.get_vision_embeds(image)
         return image_embeds, image_atts, model.get_text_embeds(text_ids, text_atts)
     main = torch.cuda.current_stream(image.device)
-    side = _side_stream(image.device)
+    side = _stream_of(_SIDE_STREAMS, image.device)
     side.wait_stream(main)
     with torch.cuda.stream(side):
         text_embeds = model.get_text_embeds(text_ids, text_atts)
@@ -147,7 +138,7 @@ class XFM(XFMBase):
         text_late = False
         if data_source != 'imagenet' and self.batch_passes and image.is_cuda and _TEXT_STREAM_ON:
             main = torch.cuda.current_stream(image.device)
-            text_stream = _side_stream(image.device)
+            text_stream = _stream_of(_SIDE_STREAMS, image.device)
             text_stream.wait_stream(main)   # (what the launch stream holds NOW: the previous step; not the ViT pass queued below)
             # _TEXT_AFTER_VIT: the text pass is QUEUED after the ViT pass (it still runs beside it, on its own stream): autograd replays
             # backward nodes in reverse order of creation, so the text tower's backward is then queued BEFORE the ViT's and runs beside
@@ -163,7 +154,7 @@ class XFM(XFMBase):
             ids_mask = ids_mask.to(device=image.device, dtype=torch.bool)
             # one 2B-row ViT pass over the B images: rows [0, B) see them clean, rows [B, 2B) MIM-masked (the token assembly reads
             # every image's patch embedding for both views)
-            mim_stream = _mim_stream(image.device) if (_MIM_STREAM and image.is_cuda) else None
+            mim_stream = _stream_of(_MIM_STREAMS, image.device) if (_MIM_STREAM and image.is_cuda) else None
             both, _, _ = self.get_vision_embeds(image, do_mask=True, split_stream=mim_stream,
                                                 ids_mask=torch.cat([torch.zeros_like(ids_mask), ids_mask], dim=0))
             if isinstance(both, tuple):

@@ -6,7 +6,7 @@ trained on (models/xfm.py:624-629).
   encoder             models/vqkd_vit.py VisionTransformer as model_vqkd.py:242-246 configures it: a plain pre-LN ViT-B, learned absolute
                       position embedding, no relative-position bias, no layer scale (init_values 0), `use_mean_pooling` -- so `norm` is the
                       identity, `fc_norm` the final LayerNorm, and `return_patch_tokens=True` (vqkd_vit.py:397-399) normalises the patch
-                      rows.  It runs on the fused trunk node of xfm_amd/vit.py with two differences: `fc_norm` is the node's final norm
+                      rows.  It runs on the fused trunk node (xfm_amd/vit_trunk.py) as xfm_amd/vit.py does, with two differences: `fc_norm` is the node's final norm
                       (the CLS row is dropped afterwards: a LayerNorm is per row), and the qkv bias is the reference's `q_bias` /
                       `v_bias` pair, composed once -- cat(q_bias, 0, v_bias), vqkd_vit.py:126 -- when the arena is built.
   encode_task_layer   Linear - Tanh - Linear to code_dim (model_vqkd.py:86-90, 155): two bf16 MFMA GEMMs with fp32 outputs.
@@ -25,7 +25,7 @@ import torch.nn as nn
 from . import functional as Fx
 from . import vit as _vit
 from .arena import LinearSlot
-from .beit2 import _Affine, _Dense
+from .vit_trunk import _Affine, _Dense
 from .norm_ema_quantizer import NormEMAVectorQuantizer
 
 IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)   # timm.data.constants
@@ -59,20 +59,8 @@ class TokenizerEncoder(_vit.VisionTransformer):
     def _final_norm(self):
         return self.fc_norm
 
-    def linear_slots(self):
-        D = self.embed_dim
-        self._slots = []
-        self._slot_patch = LinearSlot("patch_embed", [self.patch_embed.proj.weight], [self.patch_embed.proj.bias])
-        self._slot_patch.need_t = False
-        out = [self._slot_patch]
-        for i, blk in enumerate(self.blocks):
-            s = {"qkv": LinearSlot(f"blocks.{i}.qkv", [blk.attn.qkv.weight], [blk.attn.q_bias, D, blk.attn.v_bias]),
-                 "proj": LinearSlot(f"blocks.{i}.proj", [blk.attn.proj.weight], [blk.attn.proj.bias]),
-                 "fc1": LinearSlot(f"blocks.{i}.fc1", [blk.mlp.fc1.weight], [blk.mlp.fc1.bias]),
-                 "fc2": LinearSlot(f"blocks.{i}.fc2", [blk.mlp.fc2.weight], [blk.mlp.fc2.bias])}
-            self._slots.append(s)
-            out.extend(s.values())
-        return out
+    def _qkv_bias_parts(self, blk):
+        return [blk.attn.q_bias, self.embed_dim, blk.attn.v_bias]   # cat(q_bias, 0, v_bias), vqkd_vit.py:126
 
     def forward(self, x, return_patch_tokens=True):
         if not return_patch_tokens:

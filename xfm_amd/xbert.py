@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .arena import LinearSlot, OwnsArena, ParamArena
-from .beit2 import _Affine
+from .vit_trunk import _Affine
 from .decode import GenerationMixin
 from .ops import lm_head_ce, lm_head_logits
 from .xroberta import RobertaModel, _Emb, _Lin

@@ -24,9 +24,10 @@ from . import functional as Fx
 from . import marks as _marks
 from .arena import LinearSlot, ParamArena
 from . import beit2 as _beit2
-from .beit2 import _Affine, beit_base_patch16
+from .beit2 import beit_base_patch16
 from .ops import itc_loss, layer_norm, linear_ce, linear_slot, row_normalize, small_ce
 from .roberta_layer import _next_seed
+from .vit_trunk import _Affine
 from .xroberta import RobertaConfig, RobertaForMaskedLM, _Lin, rowwise
 
 BF16 = torch.bfloat16

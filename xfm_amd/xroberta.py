@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from . import functional as Fx
 from .arena import LinearSlot, OwnsArena, ParamArena, arena_note_grad, arena_note_use
-from .beit2 import _Affine
+from .vit_trunk import _Affine
 from .decode import GenerationMixin, cached_forward
 from .ops import grad_view, lm_head_ce, lm_head_logits
 from .roberta_encoder import _EncoderFn, _LastLayerRowsFn, layer_saves_maps
