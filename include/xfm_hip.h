@@ -41,7 +41,10 @@ enum { XFM_EPI_BF16 = 0, XFM_EPI_F32 = 1, XFM_EPI_GELU = 2, XFM_EPI_DGELU = 3, X
  * C = gelu(x), aux = gelu'(x) (bf16; x = the bf16-rounded pre-activation)  | C = acc * aux (the GELU dgrad, aux from the
  * forward) | fp32 C += acc.  K % 64 == 0; lda, ldb % 8 == 0.
  * tile_hint: 0 = auto, 1 = 128x128, 2 = 64x128, 3 = 64x64, 4 = 256x128 with a 3-slot LDS ring, 5 = 256x256 phase pipeline
- * (large M), 7 = 64x128 with 3 LDS stages, 8 = 64x64 with 4 (few workgroups, long K). */
+ * (large M), 6 = 320x256 one-round tile, 7 = 64x128 with 3 LDS stages, 8 = 64x64 with 4 (few workgroups, long K).
+ * 6 is never picked automatically: it is for a tall M whose 256x256 tiles spill into a nearly empty second round (25216 x 768: 297 tiles
+ * on 256 CUs, 237 of 320x256), one workgroup per tile, results bit-identical to 5.  It needs N % 256 == 0, at most one tile per CU and
+ * operands inside 32-bit element offsets; a call that is not such a shape (or any call under XFM_GEMM_NT320=0) runs as tile_hint 0. */
 int xfm_gemm_nt(const xfm_bf16* A, long lda, const xfm_bf16* B, long ldb, void* C, long ldc, const float* bias,
                 xfm_bf16* aux, long ldaux, int M, int N, int K, int epilogue, int tile_hint, void* stream);
 

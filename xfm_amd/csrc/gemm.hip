@@ -5,6 +5,7 @@
 #include <limits.h>
 #include "gemm_nt_small.hip"
 #include "gemm_nt_256.hip"
+#include "nt320_gemm.hip"
 #include "gemm_tn_small.hip"
 #include "gemm_tn_256.hip"
 #include "gemm_cast.hip"
@@ -19,15 +20,23 @@ static int nt_k_slices(int M, int N, int K) {
 }
 
 // Launch plan of xfm_gemm_nt for a shape: the tile configuration (1 = 128x128, 2 = 64x128, 3 = 64x64, 4 = 256x128 ring, 5 = 256x256
-// phase pipeline, 7 = 64x128 on 3 LDS stages, 8 = 64x64 on 4) and, for the tail split, the leading rows that run as whole rounds of
-// 256x256 tiles (rows_a > 0: those rows go to configuration 5, the rest is planned again with hint -1).  Exported as
-// xfm_gemm_nt_plan so that a profiler / benchmark can attribute a call to the kernels it launches.
+// phase pipeline, 6 = 320x256 one-round tile, 7 = 64x128 on 3 LDS stages, 8 = 64x64 on 4) and, for the tail split, the leading rows
+// that run as whole rounds of 256x256 tiles (rows_a > 0: those rows go to configuration 5, the rest is planned again with hint -1).
+// Exported as xfm_gemm_nt_plan so that a profiler / benchmark can attribute a call to the kernels it launches.
 // The leading dimensions take part: the 256x256 kernel addresses its operands with 32-bit element offsets (nt256_eligible,
 // gemm_nt_256.hip), so where the automatic plan or the tail split would pick it for operands past that range it steps down to
 // configuration 1, whose row offsets are 64-bit -- as tn_plan does with tn256_eligible.  An explicit hint 5 is left to fail in the launcher.
+// Configuration 6 (nt320_gemm.hip) is never chosen automatically: a caller whose M makes 256x256 tiles spill into a nearly empty second
+// round asks for it with hint 6, and a call that is not eligible for it (nt320_eligible: N % 256, K % 64, one round of tiles, 32-bit
+// offsets) or XFM_GEMM_NT320=0 (A/B knob) is planned as hint 0.
 static int nt_plan(int M, int N, int K, long lda, long ldb, int epi, int tile_hint, int* rows_a_out, int* k_splits_out) {
   *rows_a_out = 0;
   *k_splits_out = 1;
+  if (tile_hint == 6) {
+    static const int nt320_env = xfm_env_int("XFM_GEMM_NT320", 1);
+    if (nt320_env && nt320_eligible(M, lda, N, ldb, K)) return 6;
+    tile_hint = 0;
+  }
   int cfg = tile_hint;
   if (cfg <= 0) {  // measured on MI355X (tools/tune_gemm.py): 128x128 pays from ~3 workgroups per CU, else go smaller
     // Tail split: one workgroup per CU, so T tiles of 256x256 cost ceil(T / 256) rounds.  When the last round would be
@@ -118,6 +127,7 @@ int xfm_gemm_nt_impl(const void* A, long lda, const void* B, long ldb, void* C, 
     case 8: return launch_nt<64, 64, 4>(g, epi, st);
     case 4: return launch_nt_ring(g, epi, st);
     case 5: return launch_nt_256(g, epi, st);
+    case 6: return launch_nt_320(g, epi, st);
     default: return launch_nt<64, 64, 2>(g, epi, st);
   }
 }

@@ -196,6 +196,17 @@ def _relpos_table_grad(vit, blk, ddense, H, N, ld):
     return lambda: Fx.relpos_scatter_sorted(ddense, vit._relpos_order, vit._relpos_start, H, N, ld, dtab)
 
 
+def _nt320_hint(M, D, device):
+    """tile_hint of the trunk's five N = D projections (forward proj and fc2, the dgrads of fc1, proj and qkv) for M rows, decided
+    once per trunk pass: 6, the one-round 320 x 256 tile (csrc/nt320_gemm.hip), where 256 x 256 tiles need more than one round of the
+    CUs and 320 x 256 tiles fit in one (M = 25216: 297 against 237 tiles on 256 CUs) -- the library's plan then splits a small-tile tail
+    off every such call; 0 = the automatic plan.  XFM_GEMM_NT320=0 makes the library plan hint 6 as hint 0."""
+    if device.type != "cuda" or D % 256 != 0:
+        return 0
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    return 6 if -(-M // 320) * (D // 256) <= cus < -(-M // 256) * (D // 256) else 0
+
+
 class _TrunkFn(torch.autograd.Function):
     """All transformer blocks + the final LayerNorm as one node.  x0: fp32 [B, N, D] -> bf16 [B, N, D]."""
 
@@ -213,6 +224,7 @@ class _TrunkFn(torch.autograd.Function):
         ctx.first = (x, mean, rstd)
         ctx.nxt = nxts = [blk.norm1 for blk in blocks[1:]] + [vit._final_norm]   # the LayerNorm fused behind each block
         rel_pos = vit._rel_pos
+        ctx.nt_hint = hint = _nt320_hint(M, D, x.device)
         ahead = _biases_ahead(vit, H, N, ld, need_grad, x.device) if rel_pos and x.is_cuda and _RELPOS_AHEAD else None
         for i, blk in enumerate(blocks):
             s = vit._slots[i]
@@ -232,12 +244,12 @@ class _TrunkFn(torch.autograd.Function):
             else:
                 (ctxv, lse), ctxv_lo = Fx.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, H, N, N, blk.attn.scale, bias=dense,
                                                    bias_tiles=tiles), None
-            h1 = Fx.gemm_nt(ctxv, s["proj"].wb, s["proj"].b)
+            h1 = Fx.gemm_nt(ctxv, s["proj"].wb, s["proj"].b, tile_hint=hint)
             dp1 = None if dp is None else dp[i, 0]
             dp2 = None if dp is None else dp[i, 1]
             x1, y2, mean2, rstd2 = Fx.ln_ls_fwd(x, h1, g1, dp1, N, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
             hact, u = Fx.gemm_nt(y2, s["fc1"].wb, s["fc1"].b, epi=Fx.EPI_GELU)
-            h2 = Fx.gemm_nt(hact, s["fc2"].wb, s["fc2"].b)
+            h2 = Fx.gemm_nt(hact, s["fc2"].wb, s["fc2"].b, tile_hint=hint)
             nxt = nxts[i]
             x2, yn, meann, rstdn = Fx.ln_ls_fwd(x1, h2, g2, dp2, N, nxt.weight, nxt.bias, nxt.eps)
             saved.append((y, dense, qkv, ctxv, lse, h1, x1, mean2, rstd2, y2, u, hact, h2, x2, meann, rstdn, dp1, dp2, dense_t, ctxv_lo, tiles))
@@ -257,6 +269,7 @@ class _TrunkFn(torch.autograd.Function):
         M, H = B * N, vit.num_heads
         blocks = vit.blocks
         ld = vit._bias_ld
+        hint = ctx.nt_hint
         # two passes of one step (clean / MIM-masked view) may run on different streams; their weight gradients accumulate (+=) into the
         # same arena ranges, so a pass starts only once the previous one -- wherever it ran -- has finished
         prev = vit._trunk_bwd_done
@@ -286,11 +299,11 @@ class _TrunkFn(torch.autograd.Function):
             tn(dh2, hact, s["fc2"].dw)
             du = Fx.gemm_nt(dh2, s["fc2"].wt, epi=Fx.EPI_DGELU, aux=u, n=s["fc2"].K)
             tn(du, y2, s["fc1"].dw, dbias=s["fc1"].db)
-            dy2 = Fx.gemm_nt(du, s["fc1"].wt, n=s["fc1"].K)
+            dy2 = Fx.gemm_nt(du, s["fc1"].wt, n=s["fc1"].K, tile_hint=hint)
             dh1 = Fx.ln_ls_bwd(dy2, dstream, x1, mean2, rstd2, blk.norm2.weight, h1, g1, dp1, N, g(blk.norm2.weight),
                                g(blk.norm2.bias), s["proj"].db, dg1, defer=rq)
             tn(dh1, ctxv, s["proj"].dw)
-            dctx = Fx.gemm_nt(dh1, s["proj"].wt, n=s["proj"].K)
+            dctx = Fx.gemm_nt(dh1, s["proj"].wt, n=s["proj"].K, tile_hint=hint)
             dqkv = torch.empty_like(qkv)
             ddense = None
             if dense is not None:  # one zero fill for the whole trunk's bias-gradient scratch instead of one per block
@@ -307,7 +320,7 @@ class _TrunkFn(torch.autograd.Function):
                 else:
                     fn()
             tn(dqkv, y, s["qkv"].dw, dbias=s["qkv"].db)
-            dy = Fx.gemm_nt(dqkv, s["qkv"].wt, n=s["qkv"].K)
+            dy = Fx.gemm_nt(dqkv, s["qkv"].wt, n=s["qkv"].K, tile_hint=hint)
             ctx.saved[i] = None
             if _WGRAD_GROUP_BLOCKS > 0 and i % _WGRAD_GROUP_BLOCKS == 0:
                 wg.flush()
